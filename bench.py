@@ -10,6 +10,12 @@ backward, [gradient all-reduce over RCCL when N>1], fused AdamW, OneCycle schedu
 region (H2D excluded).  Workload at N=1: BASELINE.json configs[1] on the metric's 128x128
 pianoroll: VanillaVAE latent_dim=16, batch 256, bf16 storage / f32 accumulate (generalised
 model).  Rank 0 prints ONE JSON line.
+
+A plain run only sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`).
+--full adds the records beside it, each of which takes runs of its own: the per-kernel `roofline` (profiled steps
+with HIP events, then the same launches with side streams off), the CPU baselines and the extra records (f32 mode,
+32x32 model, drop-in loop, ELBO gap); --kernels and --dump-order read the profiled steps and so need --full.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32), before anything else runs.
 """
 import argparse
 import ctypes
@@ -25,33 +31,71 @@ sys.path.insert(0, ROOT)
 # queues, 1.39 at 6..8; without one 4..8 are the same).  Set before HIP starts.
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "6" if os.environ.get("VAE_DP_OVERLAP") == "1" else "8")   # (see torch_vae_amd/__init__.py)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec (MI355X_MICROARCH.md: 8.0 TB/s spec, 6.29 TB/s measured copy)
 MFMA_PEAK_TF = {"bf16": 2500.0, "f16": 2500.0, "f32": 157.3}
 ESZ = {"bf16": 2, "f16": 2, "f32": 4}
+DUMP_BUDGET_BYTES = 60 << 20   # --dump-outputs: all arrays together (under 64 MB with the .npy headers)
 
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--steps", type=int, default=30, help="timed steps")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also the records beside the headline number: per-kernel roofline (profiled steps), CPU baselines, extra records")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (ELBO scalars, reconstruction, parameters, gradients, BN running "
+                         "statistics) as DIR/<name>.npy")
     ap.add_argument("--size", type=int, default=128, help="pianoroll side (128 = the metric's; 32 = reference-exact model)")
     ap.add_argument("--batch", type=int, default=256, help="per-GPU batch")
     ap.add_argument("--latent", type=int, default=16)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16", "f32"])
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra records (f32 mode, 32x32 model, drop-in loop, ELBO gap)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extra records (f32 mode, 32x32 model, drop-in loop, ELBO gap)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
-    ap.add_argument("--kernels", action="store_true", help="print the per-kernel table to stderr")
+    ap.add_argument("--kernels", action="store_true", help="with --full: print the per-kernel table to stderr")
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed (RCCL) even with one rank (path test)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL (the product path); gloo only rehearses the multi-rank control flow with ranks sharing one GPU")
     ap.add_argument("--set", action="append", default=[], metavar="KNOB=VALUE", help="vae_set_option knob (diagnostics)")
-    ap.add_argument("--dump-order", default=None, help="write the per-step launch order (label, kernel symbol) as JSON")
-    return ap.parse_args()
+    ap.add_argument("--dump-order", default=None, help="with --full: write the per-step launch order (label, kernel symbol) as JSON")
+    args = ap.parse_args()
+    if (args.kernels or args.dump_order) and not args.full:
+        ap.error("--kernels and --dump-order read the profiled steps, which only --full runs")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def write_outputs(dirpath, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Write every array as <dirpath>/<name>.npy (float64 stays float64, everything else becomes float32), at most `budget`
+    bytes in all.  The budget is shared out smallest array first; an array larger than its share is replaced by a fixed,
+    seeded sample of its flattened elements (the same indices, in increasing order, on every run).  Returns
+    {name: (original shape, elements written)}."""
+    os.makedirs(dirpath, exist_ok=True)
+    arrs = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        arrs[name] = np.ascontiguousarray(a if a.dtype == np.float64 else a.astype(np.float32))
+    written, left = {}, budget
+    order = sorted(arrs, key=lambda k: arrs[k].nbytes)
+    for j, name in enumerate(order):
+        a = arrs[name]
+        keep = min(a.size, (left // (len(order) - j)) // a.itemsize)
+        if keep < a.size:
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, size=keep, replace=False))
+            out = a.reshape(-1)[idx]
+        else:
+            out = a
+        np.save(os.path.join(dirpath, name + ".npy"), out)
+        left -= out.nbytes
+        written[name] = (tuple(a.shape), int(out.size))
+    return written
 
 
 def host_cores():
@@ -223,22 +267,22 @@ def main():
     pool = SyntheticPianorollLoader(B, H, n_batches=4, seed=1000 * rank, device=dev, pool=4)
     batches = [pool.batch(i)[0] for i in range(4)]
     model.eps_seed = 7919   # (the rank is mixed into the 64-bit seed by the model: replicas draw independent noise)
-    losses = torch.zeros(3, device=dev)
+    losses, xhat = torch.zeros(3, device=dev), None
 
     def step(i):
-        out3, _ = fused_step(model, opt, batches[i % 4])
+        out3, xhat = fused_step(model, opt, batches[i % 4])
         sched.step()
-        return out3
+        return out3, xhat
 
     for i in range(args.warmup):
-        losses = step(i)
+        losses, xhat = step(i)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        losses = step(args.warmup + i)
+        losses, xhat = step(args.warmup + i)
     host_enqueue_ms = 1e3 * (time.perf_counter() - t0) / args.steps   # host time to enqueue a step (diagnostic: < ms_per_step when the GPU is the limit)
     torch.cuda.synchronize()
     if world > 1:
@@ -250,12 +294,21 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     final_loss = losses.tolist()
+    # what the last timed step handed its caller (the returned ELBO scalars and reconstruction; parameters, gradients and
+    # BatchNorm running statistics updated in place), before any further step runs
+    if args.dump_outputs and rank == 0:
+        written = write_outputs(args.dump_outputs, {
+            "elbo": losses.cpu().numpy(), "x_hat": xhat.cpu().numpy(), "parameters": model.flat_parameters().cpu().numpy(),
+            "gradients": model.flat_grads().cpu().numpy(), "bn_running_stats": model._bnflat.cpu().numpy()})
+        sampled = [f"{k} ({n} of {s})" for k, (s, n) in written.items() if n < int(np.prod(s))]
+        print(f"bench.py: wrote {len(written)} arrays to {args.dump_outputs}" + (f"; sampled: {', '.join(sampled)}" if sampled else ""),
+              file=sys.stderr, flush=True)
 
     # per-kernel durations (HIP events on each launch stream), outside the timed region.  Weight gradients run on
     # side streams concurrently with the input-gradient chain, so a launch's duration here (and in rocprofv3's
     # trace of this same command) includes the time it shares the GPU; the roofline object therefore also carries
     # the throughput of everything running inside the dominant launch's window, and the same launch measured
-    # alone (side streams off).
+    # alone (side streams off).  --full only: these steps and the figures below are not part of a plain run.
     roofline, kernels = None, []
     L_ = _lib.lib()
     h = model._ctx.handle
@@ -288,15 +341,15 @@ def main():
         ks.sort(key=lambda k: -k["ms"])
         return ks, json.loads(tbuf.value.decode()), seq
 
-    kernels, timeline, seq = profile_steps()
+    kernels, timeline, seq = profile_steps() if args.full else (None, None, None)
     # the same launches alone: side streams off for a few profiled steps (again on every rank)
     iso = None
-    if not any(kv.startswith("use_side_stream=") for kv in args.set):
+    if args.full and not any(kv.startswith("use_side_stream=") for kv in args.set):
         _lib.check(L_.vae_set_option(h, b"use_side_stream", 0), "vae_set_option")
         step(0); torch.cuda.synchronize()
         iso, _, _ = profile_steps()
         _lib.check(L_.vae_set_option(h, b"use_side_stream", 1), "vae_set_option")
-    if rank != 0:
+    if rank != 0 or not args.full:
         kernels = []
     else:
         if args.dump_order and seq is not None:
@@ -367,7 +420,7 @@ def main():
                 print(f"  {k['name']:52s} calls/step {k['calls'] // nprof:3d}  {k['ms'] / nprof:8.3f} ms/step  {k['gbs']:8.1f} GB/s  {k['tflops']:7.1f} TF", file=sys.stderr)
 
     cpu = cpu_config0 = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle.torch_cpu_step import time_cpu_baseline
         ncores, cores_how = host_cores()
         print(f"bench.py: cpu baseline on {ncores} host threads ({cores_how})", file=sys.stderr, flush=True)
@@ -388,8 +441,8 @@ def main():
 
     extras = {}
     if rank == 0:
-        print("bench.py: timed region and profiles done", file=sys.stderr, flush=True)
-    if rank == 0 and world == 1 and not args.no_extras:
+        print(f"bench.py: timed region{' and profiles' if args.full else ''} done", file=sys.stderr, flush=True)
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         extras = extra_records(args, dev, model, batches, Namespace, VanillaVAE, SyntheticPianorollLoader, build_optimizer,
                                fused_step, train_one_epoch, algorithmic_bytes_per_step, count_flops_per_sample)
     if rank == 0:
@@ -407,13 +460,13 @@ def main():
                                    f"{' (generalised bottleneck 256*(H/16)^2)' if gen else ' (reference-exact 32x32 model)'}",
                        "img_size": H, "latent_dim": L, "batch_per_gpu": B, "global_batch": B * world,
                        "parallelism": f"dp{world}", "optimizer": "AdamW+OneCycle (encoder, decoder groups)"},
-            "roofline": roofline,
             "step_roofline": {"algorithmic_bytes": step_bytes, "algorithmic_flops": step_flops,
                               "hbm_frac": round(step_bytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                               "mfma_frac": round(step_flops / (ms * 1e-3) / 1e12 / MFMA_PEAK_TF[args.dtype], 4)},
-            "cpu_baseline": cpu, "cpu_baseline_config0": cpu_config0,
             "elbo_last_step": {"loss": final_loss[0], "reconstruction_loss": final_loss[1], "kld_loss": final_loss[2]},
         }
+        if args.full:
+            out.update({"roofline": roofline, "cpu_baseline": cpu, "cpu_baseline_config0": cpu_config0})
         if world > 1 or args.force_dist:
             out["exchange"] = ("library RCCL communicator (vae_allreduce_grads)" if model.library_comm_world() == max(world, 1)
                                else f"torch.distributed ({args.backend})")

@@ -259,3 +259,34 @@ def test_bit_plane_stimuli_and_overlap_refusal(monkeypatch):
     train._refuse_overlap_on_eight_queues()
     monkeypatch.delenv("GPU_MAX_HW_QUEUES")
     train._refuse_overlap_on_eight_queues()          # HIP's own default is four
+
+
+def test_bench_write_outputs_budget_and_seeded_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: arrays that fit are written whole as float32 (float64 kept), the total stays within the budget,
+    and an array over its share is replaced by the same seeded sample of its elements on every run."""
+    import importlib.util
+    monkeypatch.setattr(sys, "path", list(sys.path))
+    monkeypatch.setenv("GPU_MAX_HW_QUEUES", os.environ.get("GPU_MAX_HW_QUEUES", "4"))   # (bench.py sets a default at import)
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(1)
+    arrays = {"small": np.arange(3, dtype=np.float64), "half": rng.standard_normal((4, 8)).astype(np.float16),
+              "big": rng.standard_normal(50000).astype(np.float32), "mid": rng.standard_normal(3000).astype(np.float32)}
+    budget = 64 * 1024
+    runs = []
+    for d in ("a", "b"):
+        written = bench.write_outputs(str(tmp_path / d), arrays, budget=budget)
+        got = {k: np.load(tmp_path / d / f"{k}.npy") for k in arrays}
+        assert sum(v.nbytes for v in got.values()) <= budget
+        runs.append((written, got))
+    (written, got), (_, again) = runs
+    assert got["small"].dtype == np.float64 and np.array_equal(got["small"], arrays["small"])
+    assert got["half"].dtype == np.float32 and np.array_equal(got["half"], arrays["half"].astype(np.float32))
+    assert got["mid"].dtype == np.float32 and np.array_equal(got["mid"], arrays["mid"])
+    assert written["mid"] == ((3000,), 3000)
+    shape, n = written["big"]
+    assert shape == (50000,) and 0 < n < 50000 and got["big"].shape == (n,)
+    assert np.isin(got["big"], arrays["big"]).all()
+    for k in arrays:
+        assert np.array_equal(got[k], again[k])

@@ -770,7 +770,7 @@ def test_bench_two_rank_control_flow():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29587", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--size", "32", "--batch", "32", "--backend", "gloo", "--no-cpu-baseline"]
+           "--size", "32", "--batch", "32", "--backend", "gloo", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -779,6 +779,35 @@ def test_bench_two_rank_control_flow():
     # (two ranks time-slice one GPU here, so a launch can take milliseconds and its GB/s round to 0.0: check the inputs)
     assert out["n_gpus"] == 2 and out["config"]["global_batch"] == 64
     assert out["roofline"]["algorithmic_bytes_per_launch"] > 0 and out["roofline"]["avg_launch_us"] > 0
+
+
+def test_bench_plain_run_dumps_last_timed_step(tmp_path):
+    """A plain bench.py run prints ONE headline line without the --full records, over exactly --steps timed steps, and
+    --dump-outputs writes what the last of them computed: its ELBO scalars are the line's elbo_last_step."""
+    import json
+    import subprocess
+    import sys
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--size", "32",
+           "--batch", "32", "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out, k
+    assert out["steps"] == 3 and out["unit"] == "samples/s" and out["higher_is_better"] is True and out["dtype"] == "bf16"
+    assert abs(out["value"] * out["ms_per_step"] / 1e3 - 32) < 0.1          # samples/s x s/step = the batch
+    for k in ("roofline", "cpu_baseline", "cpu_baseline_config0", "f32", "elbo_rel_gap", "train_one_epoch_samples_per_s"):
+        assert k not in out, k
+    files = sorted(p.name for p in (tmp_path / "out").iterdir())
+    assert files == ["bn_running_stats.npy", "elbo.npy", "gradients.npy", "parameters.npy", "x_hat.npy"]
+    got = {f[:-4]: np.load(tmp_path / "out" / f) for f in files}
+    assert sum((tmp_path / "out" / f).stat().st_size for f in files) <= 64e6
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    e = out["elbo_last_step"]
+    np.testing.assert_array_equal(got["elbo"], np.float32([e["loss"], e["reconstruction_loss"], e["kld_loss"]]))
+    assert got["x_hat"].shape == (32, 1, 32, 32) and got["parameters"].shape == got["gradients"].shape
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -8,5 +8,5 @@ done
 done
 for lib in "$@"; do
   echo "== isolated $lib"
-  VAE_STEP_LIB=$lib python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-extras --kernels --set use_side_stream=0 2>&1 >/dev/null | grep -i "wgrad\|conv_bwd_fused\|convT_bwd"
+  VAE_STEP_LIB=$lib python bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --no-extras --kernels --set use_side_stream=0 2>&1 >/dev/null | grep -i "wgrad\|conv_bwd_fused\|convT_bwd"
 done

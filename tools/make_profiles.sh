@@ -9,9 +9,9 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_${RND}_${VER}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="$ROOT/bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-extras"
+BENCH="$ROOT/bench.py --steps 30 --warmup 5 --full --no-cpu-baseline --no-extras"
 # 1. the bench line itself (with the cpu baseline and the extra records) + HIP-event tables + launch order
-python3 $ROOT/bench.py --steps 30 --warmup 5 --kernels --dump-order $OUT/order.json > $OUT/bench.json 2> $OUT/per_kernel_hip_events.txt
+python3 $ROOT/bench.py --steps 30 --warmup 5 --full --kernels --dump-order $OUT/order.json > $OUT/bench.json 2> $OUT/per_kernel_hip_events.txt
 python3 $BENCH --kernels --set use_side_stream=0 > /dev/null 2> $OUT/per_kernel_isolated.txt
 echo "bench done"
 # 2. rocprofv3 kernel trace + stats of the bench command (no counters)

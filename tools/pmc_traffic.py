@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Turn rocprofv3 PMC passes of bench.py into profiles/pmc_traffic.json (HBM bytes per launch per bench label).
 
-Usage (on the GPU box, after `bench.py --kernels --dump-order gpurun_out/order.json` and the PMC passes):
+Usage (on the GPU box, after `bench.py --full --kernels --dump-order <out>/order.json` and the PMC passes):
     python tools/pmc_traffic.py <fetch_pass_dir> <write_pass_dir> <order.json> <H> <L> <B> <dtype> [--out file.json]
 
 The two passes are separate rocprofv3 runs (`--pmc FETCH_SIZE --kernel-trace` and `--pmc WRITE_SIZE
