@@ -91,7 +91,7 @@ int vae_pre_latents(vae_ctx* ctx, float* out, vae_stream_t stream);
 int vae_last_eps(vae_ctx* ctx, float* out, vae_stream_t stream);
 
 /* VanillaVAE.loss (models.py:190-225) for the last forward: out3 = {loss, reconstruction_loss,
- * kld_loss} with kld_loss sign-flipped as at models.py:224. */
+ * kld_loss} with kld_loss sign-flipped as at models.py:224 (reconstruction term: the one that forward recorded). */
 int vae_loss(vae_ctx* ctx, float kld_weight, float* out3, vae_stream_t stream);
 /* The same scalars computed beside the backward instead of in front of it (one launch less on the critical chain):
  * enqueued on a context side stream ordered after `stream`; out3 is ordered into the caller's stream by the NEXT
@@ -105,6 +105,20 @@ int vae_loss_deferred(vae_ctx* ctx, float kld_weight, float* out3, vae_stream_t 
 int vae_elbo_generic(const float* xhat, const float* target, const float* mu, const float* log_var, int64_t n,
                      int batch, int latent_dim, float kld_weight, float* out3, float* g_xhat, float* g_mu,
                      float* g_log_var, vae_stream_t stream);
+
+/* Reconstruction term of the ELBO (models.py:208).  BCE: F.binary_cross_entropy, the reference's (default).  MSE:
+ * F.mse_loss, mean (xhat - x)^2 over B*H*W - a Gaussian likelihood for targets anywhere in [0, 1]; gradient
+ * ((xhat - x) * 2/N) * (1 - xhat) * xhat w.r.t. the logit, as ATen's mse_loss backward and sigmoid backward round it.
+ * out3 keeps its meaning: reconstruction_loss is the chosen term, loss = reconstruction_loss + kld_weight * KL. */
+#define VAE_RECON_BCE 0
+#define VAE_RECON_MSE 1
+/* reconstruction term of the ELBO for the following forwards of this context (sticky; default BCE).  A forward records
+ * the setting: its loss, deferred output conv (train = 2) and backward use the recorded term even if it changes after. */
+int vae_set_recon_loss(vae_ctx* ctx, int kind);
+/* vae_elbo_generic with the reconstruction term chosen per call (recon: VAE_RECON_*); for MSE g_xhat = (xhat - t) * 2/n. */
+int vae_elbo_generic_ex(const float* xhat, const float* target, const float* mu, const float* log_var, int64_t n,
+                        int batch, int latent_dim, float kld_weight, int recon, float* out3, float* g_xhat,
+                        float* g_mu, float* g_log_var, vae_stream_t stream);
 
 /* loss.backward() (train.py:650) for the last train-mode forward.
  *   grads: flat f32 buffer, same layout as params; every tensor is overwritten.

@@ -17,6 +17,8 @@ NUM_BN = 8
 DTYPE_F32 = 0
 DTYPE_BF16 = 1
 DTYPE_F16 = 2
+RECON_BCE = 0
+RECON_MSE = 1
 COMM_ID_BYTES = 128
 
 PARAM_NAMES = (
@@ -67,6 +69,8 @@ def lib():
     _sig(L.vae_loss, i32, [p, f32, p, p])
     _sig(L.vae_loss_deferred, i32, [p, f32, p, p])
     _sig(L.vae_elbo_generic, i32, [p, p, p, p, i64, i32, i32, f32, p, p, p, p, p])
+    _sig(L.vae_elbo_generic_ex, i32, [p, p, p, p, i64, i32, i32, f32, i32, p, p, p, p, p])
+    _sig(L.vae_set_recon_loss, i32, [p, i32])
     _sig(L.vae_backward, i32, [p, p, p, p, p, p, p, p, p, p, f32, i32, p])
     _sig(L.vae_backward_part, i32, [p, p, p, p, p, p, p, p, p, p, f32, i32, i32, p])
     _sig(L.vae_comm_stream, i32, [p, p, C.POINTER(C.c_void_p)])
@@ -98,6 +102,7 @@ def lib():
 EXPORTS = [
     "vae_last_error", "vae_abi_version", "vae_param_layout", "vae_bn_layout", "vae_create", "vae_destroy",
     "vae_workspace_bytes", "vae_forward", "vae_decode", "vae_pre_latents", "vae_last_eps", "vae_loss", "vae_loss_deferred", "vae_elbo_generic",
+    "vae_set_recon_loss", "vae_elbo_generic_ex",
     "vae_backward", "vae_backward_part", "vae_comm_stream", "vae_comm_unique_id", "vae_comm_init", "vae_comm_world",
     "vae_comm_destroy", "vae_allreduce_grads", "vae_broadcast_state", "vae_adamw_step", "vae_train_step", "vae_train_step_fused", "vae_synth_pianoroll", "vae_expand_stimuli", "vae_profile",
     "vae_profile_report", "vae_profile_sequence", "vae_profile_timeline", "vae_debug_stamps", "vae_debug_tensor",

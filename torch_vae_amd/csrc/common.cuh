@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/vae_step.h"
+
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
@@ -161,6 +163,29 @@ __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
+}
+
+// Reconstruction term of the ELBO per output pixel, a compile-time parameter of the output-conv kernels (RECON = VAE_RECON_*;
+// vae_set_recon_loss).  N = B*H*W, inv_n = 1/N; dlogit is ATen's loss backward followed by sigmoid_backward, in ATen's order:
+//   BCE: -(t*max(log xhat,-100) + (1-t)*max(log(1-xhat),-100))   dlogit = (xhat-t)/max(xhat(1-xhat),1e-12) * xhat(1-xhat) / N
+//   MSE: (xhat-t)^2                                                dlogit = ((xhat-t) * 2/N) * (1-xhat) * xhat
+// (2*inv_n is 2/N rounded once: a power-of-two scale is exact.)  The kernels sum the per-pixel term; the mean is a0 * inv_n.
+template <int RECON> __device__ __forceinline__ float recon_term(float xh, float tg) {
+    if constexpr (RECON == VAE_RECON_MSE) {
+        const float d = xh - tg;
+        return d * d;
+    } else {
+        const float l1 = fmaxf(logf(xh), -100.f), l0 = fmaxf(logf(1.f - xh), -100.f);
+        return -(tg * l1 + (1.f - tg) * l0);
+    }
+}
+template <int RECON> __device__ __forceinline__ float recon_dlogit(float xh, float tg, float inv_n) {
+    if constexpr (RECON == VAE_RECON_MSE) {
+        return (xh - tg) * (2.f * inv_n) * (1.f - xh) * xh;
+    } else {
+        const float om = xh * (1.f - xh);
+        return (xh - tg) / fmaxf(om, 1e-12f) * om * inv_n;
+    }
 }
 
 // Per-layer statistics / coefficient block, C floats per row:

@@ -695,7 +695,7 @@ static __global__ __launch_bounds__(256) void reduce_slab_kernel(const float* __
 
 
 // ---------------------------------------------------------------------------
-// Output conv forward + sigmoid + BCE + dlogit on MFMA (bf16 mode); same math as convout_fwd_kernel.
+// Output conv forward + sigmoid + reconstruction term + dlogit on MFMA (bf16 mode); same math as convout_fwd_kernel.
 //   part[p][t] = sum_c a[p][c] w[t][c]   : M = patch pixels (tile + 1-pixel halo), K = 32 channels, N = 9 taps
 //   logit[q]   = bias + sum_t part[q + off(t)][t]
 // Persistent workgroups over 8x32-pixel tiles; next tile's (8+2)x(32+2) patch of y is prefetched.
@@ -707,7 +707,7 @@ template <typename T> struct ConvOutFwdMfmaArgs {
     int rev;
 };
 
-template <typename T>
+template <typename T, int RECON>
 __global__ __launch_bounds__(256, 2) void convout_fwd_mfma_kernel(ConvOutFwdMfmaArgs<T> a) {
     typedef typename H16<T>::v8 T8;
     constexpr int TH = 8, TW = 32, PH = TH + 2, PW = TW + 2, NP = PH * PW, NPAD = 384, PITCH = 80, NCHK = NP * 4, MAXI = 6;
@@ -808,11 +808,9 @@ __global__ __launch_bounds__(256, 2) void convout_fwd_mfma_kernel(ConvOutFwdMfma
             for (int t = 0; t < 9; ++t) logit += part[((oy + t / 3) * PW + ox + t % 3) * 9 + t];
             const size_t gi = ((size_t)b * a.H + y0 + oy) * a.W + x0 + ox;
             const float xh = 1.f / (1.f + expf(-logit));
-            const float l1 = fmaxf(logf(xh), -100.f), l0 = fmaxf(logf(1.f - xh), -100.f);
-            bsum += -(tg * l1 + (1.f - tg) * l0);
-            const float om = xh * (1.f - xh);
+            bsum += recon_term<RECON>(xh, tg);
             a.xhat[gi] = xh;
-            a.dlogit[gi] = (xh - tg) / fmaxf(om, 1e-12f) * om * a.inv_n;
+            a.dlogit[gi] = recon_dlogit<RECON>(xh, tg, a.inv_n);
         }
     }
     bsum = wave_sum(bsum);
@@ -993,7 +991,7 @@ __global__ __launch_bounds__(256, 2) void convout_bwd_mfma_kernel(ConvOutBwdMfma
 // as convout_fwd_mfma_kernel followed by convout_bwd_mfma_kernel (tests/test_parity_gpu.py checks bit-identity).
 template <typename T> struct ConvOutStepArgs {
     const T* yf; const float* wt; const float* bias; const float* target;
-    float* xhat; double* accum;                 // accum[rep*8 + 0] += BCE sum, [rep*8 + 2] += sum of dlogit (bias gradient)
+    float* xhat; double* accum;                 // accum[rep*8 + 0] += reconstruction-term sum, [rep*8 + 2] += sum of dlogit (bias gradient)
     T* dz; float* slab; double* stat;           // stat: sum dz | sum dz*xhat7 of final_layer's BatchNorm (replicated)
     int B, H, W, n_tiles; float inv_n, slope, gmul;
     BnFuse fuse;                                // final_layer BatchNorm finalised in the prologue (forward mode)
@@ -1003,7 +1001,7 @@ template <typename T> struct ConvOutStepArgs {
 
 static inline size_t convout_step_lds() { return 448 * 80 + 8 * 32 * 80 + 448 * 9 * 4 + (10 * 34 + 8) * 4 + 4 * (32 * 9 + 64 + 2) * 4 + 128 * 4; }
 
-template <typename T>
+template <typename T, int RECON>
 __global__ __launch_bounds__(256, 2) void convout_step_mfma_kernel(ConvOutStepArgs<T> a) {
     typedef typename H16<T>::v8 T8;
     constexpr int TH = 8, TW = 32, PH = TH + 4, PW = TW + 4, NP = PH * PW, NPAD = 448, PITCH = 80, NCHK = NP * 4, MAXI = 7;
@@ -1113,7 +1111,7 @@ __global__ __launch_bounds__(256, 2) void convout_step_mfma_kernel(ConvOutStepAr
             }
         }
         __syncthreads();
-        // ---- logits, sigmoid, BCE and dlogit on the tile + 1-pixel halo (340 pixels)
+        // ---- logits, sigmoid, reconstruction term and dlogit on the tile + 1-pixel halo (340 pixels)
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int i = tid + 256 * u;
@@ -1124,13 +1122,11 @@ __global__ __launch_bounds__(256, 2) void convout_step_mfma_kernel(ConvOutStepAr
                 for (int t = 0; t < 9; ++t) logit += part[((ry + t / 3) * PW + rx + t % 3) * 9 + t];
                 const float tg = u ? tg1 : tg0;
                 const float xh = 1.f / (1.f + expf(-logit));
-                const float om = xh * (1.f - xh);
-                const float dlv = (xh - tg) / fmaxf(om, 1e-12f) * om * a.inv_n;
+                const float dlv = recon_dlogit<RECON>(xh, tg, a.inv_n);
                 const float dl = (u ? tk1 : tk0) ? dlv * gs : 0.f;
                 dl_s[i] = dl;
                 if (ry >= 1 && ry <= TH && rx >= 1 && rx <= TW) {   // the tile itself
-                    const float l1 = fmaxf(logf(xh), -100.f), l0 = fmaxf(logf(1.f - xh), -100.f);
-                    bsum += -(tg * l1 + (1.f - tg) * l0);
+                    bsum += recon_term<RECON>(xh, tg);
                     a.xhat[((size_t)b * a.H + y0 + ry - 1) * a.W + x0 + rx - 1] = xh;
                     sdl += dl;
                 }

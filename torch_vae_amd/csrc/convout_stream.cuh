@@ -1,4 +1,4 @@
-// Output conv of the VAE (final_layer.3: Conv2d(32 -> 1, 3x3, pad 1) + sigmoid + BCE) - forward, loss, input gradient, weight
+// Output conv of the VAE (final_layer.3: Conv2d(32 -> 1, 3x3, pad 1) + sigmoid + BCE or MSE) - forward, loss, input gradient, weight
 // gradient and the BatchNorm-backward statistics of final_layer.1 in ONE streaming pass over y7, for 128-pixel-wide images and
 // 16-bit storage (gfx950).  Same arithmetic, element for element, as convout_step_mfma_kernel (conv_mfma.cuh); what changes
 // is the walk:
@@ -18,7 +18,7 @@
 //   * a tick = 2 image rows = 8 blocks of 32 pixels and has two phases separated by raw s_barriers; the waves are split into
 //     two groups with their own code (and register allocation), one wave of each kind per SIMD and phase:
 //       phase 1  group B (waves 8..15): stage rows s, s+1 (y ring -> BatchNorm + LeakyReLU -> a ring);
-//                group A (waves 0..3):  logits / sigmoid / BCE / dlogit of rows s-3, s-2 (tap products of rows s-4 .. s-1
+//                group A (waves 0..3):  logits / sigmoid / loss term / dlogit of rows s-3, s-2 (tap products of rows s-4 .. s-1
 //                                       are in LDS since the last tick);
 //       phase 2  group B: issue the copies of tick +2; tap products of rows s, s+1; weight gradient of rows s-4, s-3;
 //                group A (waves 0..7): input gradient, epilogue and dz store of rows s-4, s-3.
@@ -79,7 +79,7 @@ static inline size_t convout_stream_lds() {
     return (size_t)(cos::NY + cos::NA) * cos::ROWB + 4 * 9 * cos::PPW * 4 + 8 * 3 * cos::DLW * 2 + cos::NTG * cos::RW * 4 + 128 * 4;
 }
 
-template <typename T>
+template <typename T, int RECON>
 __global__ __launch_bounds__(1024) void convout_stream_kernel(ConvOutStreamArgs<T> a) {
     using namespace cos;
     typedef typename H16<T>::v8 T8;
@@ -279,7 +279,7 @@ __global__ __launch_bounds__(1024) void convout_stream_kernel(ConvOutStreamArgs<
             const int b = unit / a.nb, r0 = (unit - b * a.nb) * a.RB, r1 = r0 + a.RB;
             for (int k = 0; k < K; ++k) {
                 const int s = r0 - 2 + 2 * k;
-                // ---- phase 1 (waves 0..3): logits / sigmoid / BCE / dlogit of rows s - 3, s - 2 (a wave = half a row)
+                // ---- phase 1 (waves 0..3): logits / sigmoid / loss term / dlogit of rows s - 3, s - 2 (a wave = half a row)
                 if (wave < 4) {
                     const int R = s - 3 + lrow;
                     const bool ok = R >= 0 && R < H && R >= r0 - 1 && R <= r1;
@@ -288,16 +288,14 @@ __global__ __launch_bounds__(1024) void convout_stream_kernel(ConvOutStreamArgs<
 #pragma unroll
                     for (int t = 0; t < 9; ++t) logit += part[(((p4 + lrow + t / 3) & 3) * 9 + t) * PPW + 4 + lx + t % 3 - 1];
                     const float xh = 1.f / (1.f + expf(-logit));
-                    const float om = xh * (1.f - xh);
-                    const float dlv = (xh - tg) / fmaxf(om, 1e-12f) * om * a.inv_n;
+                    const float dlv = recon_dlogit<RECON>(xh, tg, a.inv_n);
                     const float dl = ok ? dlv * gs : 0.f;
                     const T dlt = (T)dl;
                     T* drow = dlc + ((p4 + 1 + lrow) & 3) * 3 * DLW + lx + 8;
                     drow[-1] = dlt; drow[DLW] = dlt; drow[2 * DLW + 1] = dlt;
                     drow[12 * DLW - 1] = dlt; drow[13 * DLW] = dlt; drow[14 * DLW + 1] = dlt;      // the same row at slot + 4
                     if (ok && R >= r0 && R < r1) {        // the band's own rows
-                        const float l1 = fmaxf(logf(xh), -100.f), l0 = fmaxf(logf(1.f - xh), -100.f);
-                        bsum += -(tg * l1 + (1.f - tg) * l0);
+                        bsum += recon_term<RECON>(xh, tg);
                         a.xhat[((size_t)(b * H + R)) * RW + lx] = xh;
                         sdl += dl;
                     }
@@ -375,7 +373,7 @@ __global__ __launch_bounds__(1024) void convout_stream_kernel(ConvOutStreamArgs<
         }
         if (lane == 0) { red[wave][352] = sdl; red[wave][353] = bsum; }
     }
-    // ---- workgroup reductions: dW (rows = channel, lanes 0..8 = tap) from group B, statistics / sum of dlogit / BCE sum from group A
+    // ---- workgroup reductions: dW (rows = channel, lanes 0..8 = tap) from group B, statistics / sum of dlogit / loss-term sum from group A
     deep::barrier_lds();
     auto rsum = [&](int j) { float v = 0.f;
 #pragma unroll

@@ -185,9 +185,8 @@ __global__ __launch_bounds__(256) void conv1_wgrad_kernel(const float* __restric
 
 // ---------------------------------------------------------------------------
 // final_layer tail: BN+LeakyReLU (on load) -> Conv2d(32->1,k3,s1,p1) -> Sigmoid  (models.py:78-81)
-// fused with the reconstruction term of the ELBO (models.py:208) and its gradient:
-//   xhat = sigmoid(logit);  bce += -(t*max(log xhat,-100) + (1-t)*max(log(1-xhat),-100))
-//   dlogit = (xhat-t)/max(xhat(1-xhat),1e-12) * xhat(1-xhat) / N          (ATen BCE + sigmoid backward)
+// fused with the reconstruction term of the ELBO (models.py:208; BCE or MSE by RECON, common.cuh: recon_term) and its gradient:
+//   xhat = sigmoid(logit);  accum[0] += sum of the per-pixel term;  dlogit = recon_dlogit(xhat, t)
 // Tile: 32x16 outputs per workgroup; phase 1 computes per input pixel the nine
 // 32-channel dot products, phase 2 gathers the 3x3 neighbourhood from LDS.
 struct ConvOutArgs {
@@ -195,11 +194,11 @@ struct ConvOutArgs {
     const float* wt; const float* bias;     // wt [9][32] (tap-major copy of final_layer.3.weight)
     const float* target;                    // [B,H,W] (= the input x)
     float* xhat; float* dlogit;             // [B,H,W]
-    double* accum;                          // [0] bce sum
+    double* accum;                          // [0] reconstruction-term sum
     int B, H, W; float inv_n; float slope;
 };
 
-template <typename T>
+template <typename T, int RECON>
 __global__ __launch_bounds__(256) void convout_fwd_kernel(ConvOutArgs a) {
     constexpr int TH = 16, TW = 32, PH = TH + 2, PW = TW + 2, NP = PH * PW;
     __shared__ float part[NP * 9];
@@ -244,11 +243,9 @@ __global__ __launch_bounds__(256) void convout_fwd_kernel(ConvOutArgs a) {
         const size_t gi = ((size_t)b * a.H + y0 + oy) * a.W + x0 + ox;
         const float tg = a.target[gi];
         const float xh = 1.f / (1.f + expf(-logit));
-        const float l1 = fmaxf(logf(xh), -100.f), l0 = fmaxf(logf(1.f - xh), -100.f);
-        bsum += -(tg * l1 + (1.f - tg) * l0);
-        const float om = xh * (1.f - xh);
+        bsum += recon_term<RECON>(xh, tg);
         a.xhat[gi] = xh;
-        a.dlogit[gi] = (xh - tg) / fmaxf(om, 1e-12f) * om * a.inv_n;
+        a.dlogit[gi] = recon_dlogit<RECON>(xh, tg, a.inv_n);
     }
     bsum = wave_sum(bsum);
     if ((tid & 63) == 0) wred[tid >> 6] = bsum;
@@ -279,6 +276,22 @@ static __global__ void bce_kernel(const float* __restrict__ xh_, const float* __
         const float xh = xh_[i], tg = tg_[i];
         bsum += -(tg * fmaxf(logf(xh), -100.f) + (1.f - tg) * fmaxf(logf(1.f - xh), -100.f));
         if (gx) gx[i] = (xh - tg) / fmaxf(xh * (1.f - xh), 1e-12f) * inv_n;
+    }
+    bsum = wave_sum(bsum);
+    if ((threadIdx.x & 63) == 0) wred[threadIdx.x >> 6] = bsum;
+    __syncthreads();
+    if (threadIdx.x == 0) unsafeAtomicAdd(&accum[0], (double)(wred[0] + wred[1] + wred[2] + wred[3]));
+}
+
+// generic F.mse_loss(mean) forward + grad w.r.t. the prediction: (xhat-t)^2, ATen mse_loss_backward (2/N) * (xhat-t)
+static __global__ void mse_kernel(const float* __restrict__ xh_, const float* __restrict__ tg_, float* __restrict__ gx,
+                           double* __restrict__ accum, long n, float two_inv_n) {
+    __shared__ float wred[4];
+    float bsum = 0.f;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const float d = xh_[i] - tg_[i];
+        bsum += d * d;
+        if (gx) gx[i] = two_inv_n * d;
     }
     bsum = wave_sum(bsum);
     if ((threadIdx.x & 63) == 0) wred[threadIdx.x >> 6] = bsum;

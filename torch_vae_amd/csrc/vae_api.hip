@@ -365,6 +365,7 @@ extern "C" int vae_forward(vae_ctx* c, const float* x, int B, const float* param
     if (!x || !params || !xhat || !mu || !lv || !z) return vae_set_error("vae_forward", "null tensor pointer");
     hipStream_t st = (hipStream_t)stream;
     c->cur_stream = st; c->cur_stream_set = true;
+    c->fwd_recon = c->recon;
     return VAE_DISPATCH(c->dtype, forward_impl, (c, x, B, params, bn_running, nbt, eps, seed, train, xhat, mu, lv, z, st));
 }
 
@@ -374,12 +375,19 @@ extern "C" int vae_decode(vae_ctx* c, const float* z, int B, const float* params
     if (B < 1 || B > c->maxB) return vae_set_error("vae_decode", "batch exceeds the context's max_batch");
     if (!z || !params || !xhat) return vae_set_error("vae_decode", "null tensor pointer");
     hipStream_t st = (hipStream_t)stream;
-    c->B = B; c->trained = 0;   // a decode-only pass cannot be differentiated
+    c->B = B; c->trained = 0; c->fwd_recon = c->recon;   // a decode-only pass cannot be differentiated
     HIP_CHECK_RET(hipMemsetAsync(c->dstats, 0, c->n_dstats * sizeof(double), st)); c->bwd_dirty = 0;
     int rc = VAE_DISPATCH(c->dtype, pack_weights, (c, params, st));
     if (rc) return rc;
     // the reconstruction-loss side outputs of the output-conv kernel are unused here: xhat doubles as the target
     return VAE_DISPATCH(c->dtype, decode_impl, (c, z, B, params, bn_running, nbt, train, xhat, xhat, st));
+}
+
+extern "C" int vae_set_recon_loss(vae_ctx* c, int kind) {
+    if (!c) return vae_set_error("vae_set_recon_loss", "null ctx");
+    if (kind != VAE_RECON_BCE && kind != VAE_RECON_MSE) return vae_set_error("vae_set_recon_loss", "kind must be VAE_RECON_BCE or VAE_RECON_MSE");
+    c->recon = kind;
+    return 0;
 }
 
 extern "C" int vae_loss(vae_ctx* c, float kld_weight, float* out3, vae_stream_t stream) {
@@ -411,8 +419,9 @@ extern "C" int vae_loss_deferred(vae_ctx* c, float kld_weight, float* out3, vae_
 static constexpr int kGenericSlots = 64, kMaxDevices = 64;
 static double* g_generic_ring[kMaxDevices] = {nullptr};
 static unsigned g_generic_next[kMaxDevices] = {0};
-extern "C" int vae_elbo_generic(const float* xhat, const float* target, const float* mu, const float* lv, int64_t n, int B, int L,
-                                float kld_weight, float* out3, float* g_xhat, float* g_mu, float* g_lv, vae_stream_t stream) {
+extern "C" int vae_elbo_generic_ex(const float* xhat, const float* target, const float* mu, const float* lv, int64_t n, int B, int L,
+                                   float kld_weight, int recon, float* out3, float* g_xhat, float* g_mu, float* g_lv, vae_stream_t stream) {
+    if (recon != VAE_RECON_BCE && recon != VAE_RECON_MSE) return vae_set_error("vae_elbo_generic_ex", "recon must be VAE_RECON_BCE or VAE_RECON_MSE");
     hipStream_t st = (hipStream_t)stream;
     int dev = 0;
     HIP_CHECK_RET(hipGetDevice(&dev));
@@ -420,13 +429,23 @@ extern "C" int vae_elbo_generic(const float* xhat, const float* target, const fl
     if (!g_generic_ring[dev]) HIP_CHECK_RET(hipMalloc(&g_generic_ring[dev], kGenericSlots * 4 * sizeof(double)));
     double* acc = g_generic_ring[dev] + 4 * (g_generic_next[dev]++ % kGenericSlots);
     HIP_CHECK_RET(hipMemsetAsync(acc, 0, 4 * sizeof(double), st));
-    hipLaunchKernelGGL(bce_kernel, dim3((unsigned)std::min<long>((n + 255) / 256, 2048)), dim3(256), 0, st, xhat, target, g_xhat, acc, (long)n, (float)(1.0 / (double)n));
-    LAUNCH_CHECK("bce_kernel");
+    const dim3 grid((unsigned)std::min<long>((n + 255) / 256, 2048));
+    if (recon == VAE_RECON_MSE) {
+        hipLaunchKernelGGL(mse_kernel, grid, dim3(256), 0, st, xhat, target, g_xhat, acc, (long)n, (float)(2.0 / (double)n));
+        LAUNCH_CHECK("mse_kernel");
+    } else {
+        hipLaunchKernelGGL(bce_kernel, grid, dim3(256), 0, st, xhat, target, g_xhat, acc, (long)n, (float)(1.0 / (double)n));
+        LAUNCH_CHECK("bce_kernel");
+    }
     hipLaunchKernelGGL(kld_only_kernel, dim3((B * L + 255) / 256), dim3(256), 0, st, mu, lv, acc, B * L, kld_weight / (float)B, g_mu, g_lv);
     LAUNCH_CHECK("kld_only_kernel");
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, st, acc, out3, 1.0 / (double)n, 1.0 / (double)B, kld_weight, 1);
     LAUNCH_CHECK("loss_finalize_kernel");
     return 0;
+}
+extern "C" int vae_elbo_generic(const float* xhat, const float* target, const float* mu, const float* lv, int64_t n, int B, int L,
+                                float kld_weight, float* out3, float* g_xhat, float* g_mu, float* g_lv, vae_stream_t stream) {
+    return vae_elbo_generic_ex(xhat, target, mu, lv, n, B, L, kld_weight, VAE_RECON_BCE, out3, g_xhat, g_mu, g_lv, stream);
 }
 
 // A non-blocking stream owned by the context, ordered after everything enqueued on `stream` so far.  Work the caller

@@ -77,7 +77,7 @@ struct vae_ctx {
     hipStream_t comm; hipEvent_t ev_comm; int comm_busy;   // stream lent to the caller for the mid-backward gradient all-reduce (vae_comm_stream)
     void* nccl_comm = nullptr; int comm_rank = 0, comm_world = 0;   // RCCL communicator owned by the context (vae_comm.hip)
     int use_side_stream, knob_bwd_per_cu, knob_wave_nt_max, knob_lay22_min_nt, knob_down_waves, knob_pack_grid, knob_xcd_map, knob_up_nt_max, knob_lay42, knob_wgrad_layer_wgs, knob_conv1_grid, use_fused_bn, knob_rev, knob_lean, walk_dir, bwd_dirty, bwd_half_done;
-    double* dstats; size_t n_dstats; double* accum;  // accum: [0] bce, [1] kl term, [2] sum dlogit
+    double* dstats; size_t n_dstats; double* accum;  // accum: [0] reconstruction term (BCE / MSE sum), [1] kl term, [2] sum dlogit
     double* generic_accum;                           // vae_elbo_generic on this context's device (per context, not process-global)
     WgradKnobs wk;
     float* reduce_tmp = nullptr; size_t reduce_tmp_floats = 0; unsigned reduce_slot = 0;   // partial sums of the two-level slab reduction
@@ -116,6 +116,9 @@ struct vae_ctx {
     int use_convout_stream = 1, knob_convout_bands = 0;   // (bands per image: 0 = chosen by the launcher)
     int knob_convout_step_grid = 1024;   // (= knob_convout_bwd_grid: with the same tile partition the fused kernel and convout_bwd produce bit-identical statistics)
     BnFuse pending_f7; float* loss_out3 = nullptr; float loss_kw = 0.f;
+    // reconstruction term of the ELBO (VAE_RECON_*): recon is the setting for the following forwards (vae_set_recon_loss);
+    // fwd_recon is what the last forward was run with - its deferred output conv, loss and backward use that one
+    int recon = VAE_RECON_BCE, fwd_recon = VAE_RECON_BCE;
     int use_fused_wgrad = 3, knob_fused_grid = 256, use_recomp_dz = 0;   // use_fused_wgrad: bit 0 decoder (ConvT) kernels, bit 1 encoder.1 kernel
     // f16 storage: the backward runs on gradients multiplied by gmul (a power of two chosen per forward so that the stored
     // dz stay inside the f16 range: the BCE mean makes them O(1/(B*H*W))); every parameter gradient is written times ginv.

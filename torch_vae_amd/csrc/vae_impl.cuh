@@ -501,6 +501,7 @@ int decode_impl(vae_ctx* c, const float* z, int B, const float* params, float* b
             return 0;
         }
         ProfScope ps(c, "convout_fwd+bce", ((double)sizeof(T) * 32 + 12.0) * B * H * H, 2.0 * 9 * 32 * B * H * H, st);
+        const bool mse = c->fwd_recon == VAE_RECON_MSE;
         bool launched = false;
         if constexpr (sizeof(T) == 2) {
             if (mfma_out) {
@@ -508,11 +509,17 @@ int decode_impl(vae_ctx* c, const float* z, int B, const float* params, float* b
                 m.yf = reinterpret_cast<const T*>(c->lay[7].y); m.coef = a.coef; m.wt = a.wt; m.bias = a.bias; m.target = x;
                 m.xhat = xhat; m.dlogit = c->dlogit; m.accum = c->accum; m.B = B; m.H = H; m.W = H; m.n_tiles = B * (H / 8) * (H / 32);
                 m.inv_n = a.inv_n; m.slope = kSlope;
-                hipLaunchKernelGGL((convout_fwd_mfma_kernel<T>), dim3(std::min(m.n_tiles, c->knob_convout_grid)), dim3(256), 0, st, m);
+                const dim3 grid(std::min(m.n_tiles, c->knob_convout_grid));
+                if (mse) hipLaunchKernelGGL((convout_fwd_mfma_kernel<T, VAE_RECON_MSE>), grid, dim3(256), 0, st, m);
+                else hipLaunchKernelGGL((convout_fwd_mfma_kernel<T, VAE_RECON_BCE>), grid, dim3(256), 0, st, m);
                 launched = true;
             }
         }
-        if (!launched) hipLaunchKernelGGL((convout_fwd_kernel<T>), dim3(B * (H / 16) * (H / 32)), dim3(256), 0, st, a);
+        if (!launched) {
+            const dim3 grid(B * (H / 16) * (H / 32));
+            if (mse) hipLaunchKernelGGL((convout_fwd_kernel<T, VAE_RECON_MSE>), grid, dim3(256), 0, st, a);
+            else hipLaunchKernelGGL((convout_fwd_kernel<T, VAE_RECON_BCE>), grid, dim3(256), 0, st, a);
+        }
         LAUNCH_CHECK("convout_fwd_kernel");
     }
     return 0;
@@ -754,8 +761,13 @@ static int backward_first(vae_ctx* c, const float* x, const float* params, float
                 m.nb = nb; m.RB = H / nb; m.n_units = B * nb;
                 grid = std::min(m.n_units, ncu);
                 const size_t lds = convout_stream_lds();
-                if (set_lds(convout_stream_kernel<T>, lds)) return -1;
-                hipLaunchKernelGGL((convout_stream_kernel<T>), dim3(grid), dim3(1024), lds, st, m);
+                if (c->fwd_recon == VAE_RECON_MSE) {
+                    if (set_lds(convout_stream_kernel<T, VAE_RECON_MSE>, lds)) return -1;
+                    hipLaunchKernelGGL((convout_stream_kernel<T, VAE_RECON_MSE>), dim3(grid), dim3(1024), lds, st, m);
+                } else {
+                    if (set_lds(convout_stream_kernel<T, VAE_RECON_BCE>, lds)) return -1;
+                    hipLaunchKernelGGL((convout_stream_kernel<T, VAE_RECON_BCE>), dim3(grid), dim3(1024), lds, st, m);
+                }
                 launched = true;
                 c->convout_pending = 0;
             }
@@ -767,8 +779,13 @@ static int backward_first(vae_ctx* c, const float* x, const float* params, float
                 m.inv_n = (float)(1.0 / ((double)B * H * H)); m.slope = kSlope; m.gmul = c->gmul; m.ablate = c->knob_ablate_f;
                 grid = std::min(m.n_tiles, c->knob_convout_step_grid);   // 512 resident (2 per CU by LDS): two full rounds
                 const size_t lds = convout_step_lds();
-                if (set_lds(convout_step_mfma_kernel<T>, lds)) return -1;
-                hipLaunchKernelGGL((convout_step_mfma_kernel<T>), dim3(grid), dim3(256), lds, st, m);
+                if (c->fwd_recon == VAE_RECON_MSE) {
+                    if (set_lds(convout_step_mfma_kernel<T, VAE_RECON_MSE>, lds)) return -1;
+                    hipLaunchKernelGGL((convout_step_mfma_kernel<T, VAE_RECON_MSE>), dim3(grid), dim3(256), lds, st, m);
+                } else {
+                    if (set_lds(convout_step_mfma_kernel<T, VAE_RECON_BCE>, lds)) return -1;
+                    hipLaunchKernelGGL((convout_step_mfma_kernel<T, VAE_RECON_BCE>), dim3(grid), dim3(256), lds, st, m);
+                }
                 launched = true;
                 c->convout_pending = 0;
             }

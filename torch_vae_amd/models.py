@@ -19,6 +19,11 @@ Deviations from the reference, all explicit:
     256*(input_dim/16)^2 instead of the hard-wired 1024 (models.py:33,166).
   * gradients are written to ``param.grad`` by the backward kernel directly
     (no AccumulateGrad hooks fire).
+  * ``recon_loss="mse"`` (keyword-only; default ``"bce"``, the reference's
+    models.py:208) replaces the reconstruction term of the ELBO by
+    ``F.mse_loss(xhat, x)`` - a Gaussian likelihood for velocity-valued rolls
+    with targets anywhere in [0, 1].  ``model.recon_loss`` may be reassigned; it
+    is read at every forward and fused step.  ``loss()`` keys are unchanged.
 """
 from __future__ import annotations
 
@@ -35,6 +40,16 @@ from .types_helpers import EncoderOutput, LossOutput, ModelOutput
 _DTYPES = {"f32": _lib.DTYPE_F32, "fp32": _lib.DTYPE_F32, "float32": _lib.DTYPE_F32,
            "bf16": _lib.DTYPE_BF16, "bfloat16": _lib.DTYPE_BF16,
            "f16": _lib.DTYPE_F16, "fp16": _lib.DTYPE_F16, "float16": _lib.DTYPE_F16, "half": _lib.DTYPE_F16}
+
+
+_RECON = {"bce": _lib.RECON_BCE, "mse": _lib.RECON_MSE}
+
+
+def _recon_kind(name) -> int:
+    kind = _RECON.get(name) if isinstance(name, str) else None
+    if kind is None:
+        raise ValueError(f"recon_loss must be one of {sorted(_RECON)}, got {name!r}")
+    return kind
 
 
 _NULL_GUARD = contextlib.nullcontext()
@@ -57,6 +72,12 @@ class _Context:
         self.handle = _lib.lib().vae_create(img_size, latent_dim, max_batch, dtype, int(generalised))
         if not self.handle:
             raise _lib.VaeLibError("vae_create: " + _lib.lib().vae_last_error().decode())
+        self.recon = _lib.RECON_BCE     # the library's default (vae_set_recon_loss)
+
+    def set_recon(self, kind: int):
+        if kind != self.recon:
+            _lib.check(_lib.lib().vae_set_recon_loss(self.handle, kind), "vae_set_recon_loss")
+            self.recon = kind
 
     def __del__(self):
         try:
@@ -112,15 +133,15 @@ class _GenericELBO(torch.autograd.Function):
     """VanillaVAE.loss on tensors that are not the model's own last forward."""
 
     @staticmethod
-    def forward(ctx, xhat, target, mu, lv, kld_weight):
+    def forward(ctx, xhat, target, mu, lv, kld_weight, recon):
         xhat, target, mu, lv = (t.contiguous().float() for t in (xhat, target, mu, lv))
         out3 = torch.empty(3, device=xhat.device, dtype=torch.float32)
         gx, gm, gl = torch.empty_like(xhat), torch.empty_like(mu), torch.empty_like(lv)
         with torch.cuda.device(xhat.device):
-            _lib.check(_lib.lib().vae_elbo_generic(xhat.data_ptr(), target.data_ptr(), mu.data_ptr(), lv.data_ptr(),
-                                                  xhat.numel(), mu.shape[0], mu.shape[1], float(kld_weight),
-                                                  out3.data_ptr(), gx.data_ptr(), gm.data_ptr(), gl.data_ptr(),
-                                                  _stream_ptr(xhat.device)), "vae_elbo_generic")
+            _lib.check(_lib.lib().vae_elbo_generic_ex(xhat.data_ptr(), target.data_ptr(), mu.data_ptr(), lv.data_ptr(),
+                                                     xhat.numel(), mu.shape[0], mu.shape[1], float(kld_weight), int(recon),
+                                                     out3.data_ptr(), gx.data_ptr(), gm.data_ptr(), gl.data_ptr(),
+                                                     _stream_ptr(xhat.device)), "vae_elbo_generic_ex")
         ctx.save_for_backward(gx, gm, gl)
         ctx.mark_non_differentiable(out3)
         return out3[0].clone(), out3
@@ -128,7 +149,7 @@ class _GenericELBO(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, _g_out3):
         gx, gm, gl = ctx.saved_tensors
-        return gx * g_loss, None, gm * g_loss, gl * g_loss, None
+        return gx * g_loss, None, gm * g_loss, gl * g_loss, None, None
 
 
 class VanillaVAE(nn.Module):
@@ -145,6 +166,7 @@ class VanillaVAE(nn.Module):
         *,
         generalised: bool | None = None,
         compute_dtype: str = "bf16",
+        recon_loss: str = "bce",
         max_batch: int | None = None,
     ):
         super().__init__()
@@ -167,6 +189,8 @@ class VanillaVAE(nn.Module):
         if compute_dtype not in _DTYPES:
             raise ValueError(f"compute_dtype must be one of {sorted(_DTYPES)}")
         self.compute_dtype = compute_dtype
+        _recon_kind(recon_loss)
+        self.recon_loss = recon_loss
         s = self.img_size // 16 if self.generalised else 2
         self.last_conv_size = s * s  # models.py:33 hard-wires 4
         self.flattened_size = self.last_conv_size * hidden_dims[-1]
@@ -335,6 +359,7 @@ class VanillaVAE(nn.Module):
                 if getattr(self, "_want_lib_comm", False):
                     self._init_library_comm()
             self._max_batch = need
+        self._ctx.set_recon(_recon_kind(self.recon_loss))
         return self._ctx
 
     # -- data parallel: the step library's own RCCL communicator (include/vae_step.h: vae_comm_*) ----------------------
@@ -546,7 +571,7 @@ class VanillaVAE(nn.Module):
             loss = out3[0].clone()
         else:
             loss, out3 = _GenericELBO.apply(output["output"], output["input"], output["encoded"]["mu"],
-                                            output["encoded"]["log_var"], self.kld_weight)
+                                            output["encoded"]["log_var"], self.kld_weight, _recon_kind(self.recon_loss))
         return LossOutput(loss=loss, reconstruction_loss=out3[1].detach(), kld_loss=out3[2].detach())
 
     def sample(self, num_samples: int, current_device: int, **kwargs) -> Tensor:
