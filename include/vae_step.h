@@ -120,6 +120,21 @@ int vae_elbo_generic_ex(const float* xhat, const float* target, const float* mu,
                         int batch, int latent_dim, float kld_weight, int recon, float* out3, float* g_xhat,
                         float* g_mu, float* g_log_var, vae_stream_t stream);
 
+/* Importance-weighted log-likelihood (IWAE_K) and per-sample ELBO of x under the model in eval mode.
+ * eps [K,B,L] f32 or NULL (device counter generator, seed, stream 6; index (k*B+b)*L+l).
+ * Decodes `chunk` draws of the whole batch per pass: chunk*batch <= max_batch.
+ * log_w [K,B], log_likelihood [B], elbo [B]: f64, nats; log_w may be NULL.
+ *   log_w[k,b]        = log p(x_b|z_kb) + log p(z_kb) - log q(z_kb|x_b),  z_kb = eps_kb * exp(0.5 log_var_b) + mu_b
+ *   log_likelihood[b] = logsumexp_k log_w[k,b] - log K
+ *   elbo[b]           = mean_k log p(x_b|z_kb) - KL(q(z|x_b) || N(0, I))
+ * log p(x|z) follows the context's reconstruction term (vae_set_recon_loss): BCE - Bernoulli, sum over pixels of
+ * t log xhat + (1-t) log(1-xhat) with the logs clamped at -100 (normalised only for 0/1 targets); MSE - Gaussian of variance 1/2,
+ * -sum (xhat - t)^2 - (H*W/2) log(pi).  BatchNorm uses (and never writes) the running statistics in bn_running.  Nothing is
+ * left to differentiate: vae_loss / vae_backward after this call fail until the next forward. */
+int vae_log_likelihood(vae_ctx* ctx, const float* x, int batch, const float* params, const float* bn_running,
+                       int num_samples, int chunk, const float* eps, uint64_t seed,
+                       double* log_w, double* log_likelihood, double* elbo, vae_stream_t stream);
+
 /* loss.backward() (train.py:650) for the last train-mode forward.
  *   grads: flat f32 buffer, same layout as params; every tensor is overwritten.
  *   use_std: 1 adds the gradient of the standard ELBO of vae_loss (reconstruction term fused in

@@ -699,15 +699,18 @@ static __global__ __launch_bounds__(256) void reduce_slab_kernel(const float* __
 //   part[p][t] = sum_c a[p][c] w[t][c]   : M = patch pixels (tile + 1-pixel halo), K = 32 channels, N = 9 taps
 //   logit[q]   = bias + sum_t part[q + off(t)][t]
 // Persistent workgroups over 8x32-pixel tiles; next tile's (8+2)x(32+2) patch of y is prefetched.
+// PS (per-sample mode, vae_log_likelihood): the target of image b is target[b mod tB]; each tile's sum of the per-pixel term is
+// reduced in the workgroup and stored to part[tile] (tile = (b * H/8 + ty) * W/32 + tx) - no atomics, no xhat / dlogit stores.
 template <typename T> struct ConvOutFwdMfmaArgs {
     const T* yf; const float* coef; const float* wt; const float* bias; const float* target;
     float* xhat; float* dlogit; double* accum;
     int B, H, W, n_tiles; float inv_n, slope;
     BnFuse fuse;
     int rev;
+    double* part; int tB;                       // per-sample mode only
 };
 
-template <typename T, int RECON>
+template <typename T, int RECON, bool PS = false>
 __global__ __launch_bounds__(256, 2) void convout_fwd_mfma_kernel(ConvOutFwdMfmaArgs<T> a) {
     typedef typename H16<T>::v8 T8;
     constexpr int TH = 8, TW = 32, PH = TH + 2, PW = TW + 2, NP = PH * PW, NPAD = 384, PITCH = 80, NCHK = NP * 4, MAXI = 6;
@@ -741,7 +744,8 @@ __global__ __launch_bounds__(256, 2) void convout_fwd_mfma_kernel(ConvOutFwdMfma
     // chunk id = tid + 256u: patch pixel id>>2, channel quarter id&3 = tid&3 - the same quarter for every chunk of a thread
     auto prefetch = [&](int tile) {
         int b, y0, x0; tile_origin(tile, b, y0, x0);
-        pretg = a.target[((size_t)b * a.H + y0 + (tid >> 5)) * a.W + x0 + (tid & 31)];
+        const int tb = PS ? b % a.tB : b;
+        pretg = a.target[((size_t)tb * a.H + y0 + (tid >> 5)) * a.W + x0 + (tid & 31)];
         const int base = ((b * a.H + y0 - 1) * a.W + x0 - 1) * 32 + (tid & 3) * 8;
 #pragma unroll
         for (int u = 0; u < MAXI; ++u) {
@@ -808,15 +812,25 @@ __global__ __launch_bounds__(256, 2) void convout_fwd_mfma_kernel(ConvOutFwdMfma
             for (int t = 0; t < 9; ++t) logit += part[((oy + t / 3) * PW + ox + t % 3) * 9 + t];
             const size_t gi = ((size_t)b * a.H + y0 + oy) * a.W + x0 + ox;
             const float xh = 1.f / (1.f + expf(-logit));
-            bsum += recon_term<RECON>(xh, tg);
-            a.xhat[gi] = xh;
-            a.dlogit[gi] = recon_dlogit<RECON>(xh, tg, a.inv_n);
+            if constexpr (PS) {
+                // (wred is next written after two more barriers, which thread 0 reaches only after this read)
+                const float ts = wave_sum(recon_term<RECON>(xh, tg));
+                if (lane == 0) wred[wave] = ts;
+                __syncthreads();
+                if (tid == 0) a.part[(b * tiles_y + y0 / TH) * tiles_x + x0 / TW] = (double)wred[0] + (double)wred[1] + (double)wred[2] + (double)wred[3];
+            } else {
+                bsum += recon_term<RECON>(xh, tg);
+                a.xhat[gi] = xh;
+                a.dlogit[gi] = recon_dlogit<RECON>(xh, tg, a.inv_n);
+            }
         }
     }
-    bsum = wave_sum(bsum);
-    if (lane == 0) wred[wave] = bsum;
-    __syncthreads();
-    if (tid == 0) unsafeAtomicAdd(&a.accum[stat_rep() * 8 + 0], (double)(wred[0] + wred[1] + wred[2] + wred[3]));
+    if constexpr (!PS) {
+        bsum = wave_sum(bsum);
+        if (lane == 0) wred[wave] = bsum;
+        __syncthreads();
+        if (tid == 0) unsafeAtomicAdd(&a.accum[stat_rep() * 8 + 0], (double)(wred[0] + wred[1] + wred[2] + wred[3]));
+    }
 }
 
 // ---------------------------------------------------------------------------

@@ -189,6 +189,8 @@ __global__ __launch_bounds__(256) void conv1_wgrad_kernel(const float* __restric
 //   xhat = sigmoid(logit);  accum[0] += sum of the per-pixel term;  dlogit = recon_dlogit(xhat, t)
 // Tile: 32x16 outputs per workgroup; phase 1 computes per input pixel the nine
 // 32-channel dot products, phase 2 gathers the 3x3 neighbourhood from LDS.
+// PS (per-sample mode, vae_log_likelihood): target of image b is target[b mod tB]; the workgroup's sum of the per-pixel term is
+// stored to part[blockIdx.x] (= (b * H/16 + ty) * W/32 + tx) - no atomics, no xhat / dlogit stores.
 struct ConvOutArgs {
     const void* yf; const float* coef;      // [B,H,W,32] T, rows sc,0,sh
     const float* wt; const float* bias;     // wt [9][32] (tap-major copy of final_layer.3.weight)
@@ -196,9 +198,10 @@ struct ConvOutArgs {
     float* xhat; float* dlogit;             // [B,H,W]
     double* accum;                          // [0] reconstruction-term sum
     int B, H, W; float inv_n; float slope;
+    double* part; int tB;                   // per-sample mode only
 };
 
-template <typename T, int RECON>
+template <typename T, int RECON, bool PS = false>
 __global__ __launch_bounds__(256) void convout_fwd_kernel(ConvOutArgs a) {
     constexpr int TH = 16, TW = 32, PH = TH + 2, PW = TW + 2, NP = PH * PW;
     __shared__ float part[NP * 9];
@@ -206,7 +209,7 @@ __global__ __launch_bounds__(256) void convout_fwd_kernel(ConvOutArgs a) {
     const int tid = threadIdx.x;
     const int tiles_x = a.W / TW, tiles_y = a.H / TH;
     const int tile = blockIdx.x, tx = tile % tiles_x, ty = (tile / tiles_x) % tiles_y, b = tile / (tiles_x * tiles_y);
-    const int y0 = ty * TH, x0 = tx * TW;
+    const int y0 = ty * TH, x0 = tx * TW, tb = PS ? b % a.tB : b;
     const T* yf = reinterpret_cast<const T*>(a.yf);
     for (int pix = tid; pix < NP; pix += 256) {
         const int py = pix / PW, px = pix - py * PW, gy = y0 + py - 1, gx = x0 + px - 1;
@@ -241,16 +244,22 @@ __global__ __launch_bounds__(256) void convout_fwd_kernel(ConvOutArgs a) {
 #pragma unroll
         for (int t = 0; t < 9; ++t) logit += part[((oy + t / 3) * PW + ox + t % 3) * 9 + t];
         const size_t gi = ((size_t)b * a.H + y0 + oy) * a.W + x0 + ox;
-        const float tg = a.target[gi];
+        const float tg = a.target[((size_t)tb * a.H + y0 + oy) * a.W + x0 + ox];
         const float xh = 1.f / (1.f + expf(-logit));
         bsum += recon_term<RECON>(xh, tg);
-        a.xhat[gi] = xh;
-        a.dlogit[gi] = recon_dlogit<RECON>(xh, tg, a.inv_n);
+        if constexpr (!PS) {
+            a.xhat[gi] = xh;
+            a.dlogit[gi] = recon_dlogit<RECON>(xh, tg, a.inv_n);
+        }
     }
     bsum = wave_sum(bsum);
     if ((tid & 63) == 0) wred[tid >> 6] = bsum;
     __syncthreads();
-    if (tid == 0) unsafeAtomicAdd(&a.accum[stat_rep() * 8 + 0], (double)(wred[0] + wred[1] + wred[2] + wred[3]));
+    if constexpr (PS) {
+        if (tid == 0) a.part[blockIdx.x] = (double)wred[0] + (double)wred[1] + (double)wred[2] + (double)wred[3];
+    } else {
+        if (tid == 0) unsafeAtomicAdd(&a.accum[stat_rep() * 8 + 0], (double)(wred[0] + wred[1] + wred[2] + wred[3]));
+    }
 }
 
 // dlogit = g_xhat * xhat*(1-xhat) [+ gscale * dlogit_std]: caller-supplied dL/dxhat, optionally on top
@@ -903,6 +912,11 @@ __device__ __forceinline__ double counter_uniform(unsigned long long i, unsigned
     base = splitmix64(base ^ (stream * 0xD1342543DE82EF95ULL));
     const unsigned long long bits = splitmix64(base + i * 0x2545F4914F6CDD1DULL);
     return (double)(bits >> 11) * (1.0 / 9007199254740992.0);
+}
+// element i of N(0,1) stream `stream`, the arithmetic of counter_normal_kernel (= oracle.counter_normal(n, seed, stream)[i])
+__device__ __forceinline__ float counter_normal_at(unsigned long long i, unsigned long long seed, unsigned long long stream) {
+    const double u1 = counter_uniform(i, seed, 2 * stream + 1000003ULL), u2 = counter_uniform(i, seed, 2 * stream + 1000004ULL);
+    return (float)(sqrt(-2.0 * log(1.0 - u1)) * cos(2.0 * 3.14159265358979323846 * u2));
 }
 // eps ~ N(0,1): Box-Muller on the counter generator (same as oracle.counter_normal(n, seed, 5))
 static __global__ void counter_normal_kernel(float* out, long n, unsigned long long seed, unsigned long long stream) {

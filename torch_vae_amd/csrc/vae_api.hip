@@ -4,6 +4,7 @@
 #include <mutex>
 #include "vae_ctx.h"
 #include "edge_kernels.cuh"
+#include "loglik.cuh"
 
 static thread_local std::string g_err;
 int vae_set_error(const char* what, const char* why) {
@@ -82,6 +83,7 @@ extern "C" void vae_destroy(vae_ctx* c) {
     if (!c) return;
     (void)vae_comm_destroy(c);
     for (void* p : c->allocs) (void)hipFree(p);
+    if (c->ll_kb) (void)hipFree(c->ll_kb);
     if (c->n_side_ok) {
         // (the streams belong to the device pool; work of this context still on them is drained first)
         for (int i = 0; i < vae_ctx::NSIDE; ++i) { (void)hipStreamSynchronize(c->side[i]); (void)hipEventDestroy(c->ev_join[i]); }
@@ -381,6 +383,67 @@ extern "C" int vae_decode(vae_ctx* c, const float* z, int B, const float* params
     if (rc) return rc;
     // the reconstruction-loss side outputs of the output-conv kernel are unused here: xhat doubles as the target
     return VAE_DISPATCH(c->dtype, decode_impl, (c, z, B, params, bn_running, nbt, train, xhat, xhat, st));
+}
+
+// Importance-weighted log-likelihood and per-sample ELBO (loglik.cuh).  One eval-mode encoder pass; then per chunk of draws
+// the latent kernel, an eval-mode decoder pass whose output conv runs in its per-sample mode, and the first half of the combine;
+// the second half once at the end.  Leaves no forward behind: vae_loss / vae_backward afterwards fail.
+extern "C" int vae_log_likelihood(vae_ctx* c, const float* x, int B, const float* params, const float* bn_running, int K, int chunk,
+                                  const float* eps, uint64_t seed, double* log_w, double* ll, double* elbo, vae_stream_t stream) {
+    if (!c) return vae_set_error("vae_log_likelihood", "null ctx");
+    if (!x || !params || !bn_running || !ll || !elbo) return vae_set_error("vae_log_likelihood", "null tensor pointer");
+    if (B < 1 || B > c->maxB) return vae_set_error("vae_log_likelihood", "batch exceeds the context's max_batch");
+    if (K < 1 || chunk < 1) return vae_set_error("vae_log_likelihood", "num_samples and chunk must be >= 1");
+    if ((int64_t)chunk * B > c->maxB) return vae_set_error("vae_log_likelihood", "chunk * batch exceeds the context's max_batch");
+    hipStream_t st = (hipStream_t)stream;
+    const int L = c->L, H = c->H;
+    const size_t maxB = (size_t)c->maxB;
+    if (!c->ll_f) {
+        c->ll_f = dalloc<float>(c, 4 * maxB * L);
+        c->ll_part = dalloc<double>(c, maxB * (size_t)H * H / 256);   // tiles of 8x32 pixels or larger
+        c->ll_lat = dalloc<double>(c, maxB);
+        if (!c->ll_f || !c->ll_part || !c->ll_lat) return vae_set_error("vae_log_likelihood", "hipMalloc failed");
+    }
+    const size_t kb = (size_t)K * B;
+    if (c->ll_kb_n < 2 * kb) {
+        if (c->ll_kb) { HIP_CHECK_RET(hipDeviceSynchronize()); HIP_CHECK_RET(hipFree(c->ll_kb)); c->ll_kb = nullptr; c->ll_kb_n = 0; }
+        void* p = nullptr;
+        HIP_CHECK_RET(hipMalloc(&p, 2 * kb * sizeof(double)));
+        c->ll_kb = reinterpret_cast<double*>(p); c->ll_kb_n = 2 * kb;
+    }
+    float* mu = c->ll_f; float* lv = mu + maxB * L; float* z0 = lv + maxB * L; float* zc = z0 + maxB * L;
+    double* lpx = c->ll_kb; double* lw = log_w ? log_w : c->ll_kb + kb;
+    // whatever happens below, the context is left without a forward to differentiate or score
+    struct Reset { vae_ctx* c; ~Reset() { c->ps_part = nullptr; c->B = 0; c->trained = 0; c->dlogit_valid = 0; c->convout_pending = 0; } } reset{c};
+    c->cur_stream = st; c->cur_stream_set = true;
+    c->fwd_recon = c->recon;
+    float* bnr = const_cast<float*>(bn_running);   // eval mode: read only
+    int rc = VAE_DISPATCH(c->dtype, encode_impl, (c, x, B, params, bnr, nullptr, nullptr, seed, 0, mu, lv, z0, st));
+    if (rc) return rc;
+    const double cst = c->fwd_recon == VAE_RECON_MSE ? 0.5 * H * H * log(3.14159265358979323846) : 0.0;
+    for (int k0 = 0; k0 < K; k0 += chunk) {
+        const int nk = std::min(chunk, K - k0), R = nk * B;
+        IwLatentArgs la; la.mu = mu; la.lv = lv; la.eps = eps; la.z = zc; la.lat = c->ll_lat; la.B = B; la.L = L; la.k0 = k0; la.nk = nk;
+        la.seed = (unsigned long long)seed;
+        {
+            ProfScope ps(c, "iw_latent", 4.0 * R * L * (eps ? 2 : 1) + 8.0 * R, 0, st);
+            hipLaunchKernelGGL(iw_latent_kernel, dim3((R + 255) / 256), dim3(256), 0, st, la);
+            LAUNCH_CHECK("iw_latent_kernel");
+        }
+        c->ps_part = c->ll_part; c->ps_tb = B; c->ps_ntile = 0;
+        rc = VAE_DISPATCH(c->dtype, decode_impl, (c, zc, R, params, bnr, nullptr, 0, x, nullptr, st));
+        c->ps_part = nullptr;
+        if (rc) return rc;
+        if (c->ps_ntile < 1) return vae_set_error("vae_log_likelihood", "the output conv did not run in its per-sample mode");
+        ProfScope ps(c, "loglik_rows", 8.0 * R * (c->ps_ntile + 3), 0, st);
+        hipLaunchKernelGGL(loglik_rows_kernel, dim3((R + 255) / 256), dim3(256), 0, st, c->ll_part, c->ps_ntile, c->ll_lat, R,
+                           (long)k0 * B, cst, lpx, lw);
+        LAUNCH_CHECK("loglik_rows_kernel");
+    }
+    ProfScope ps(c, "loglik_final", 16.0 * kb, 0, st);
+    hipLaunchKernelGGL(loglik_final_kernel, dim3((B + 255) / 256), dim3(256), 0, st, lpx, lw, mu, lv, K, B, L, ll, elbo);
+    LAUNCH_CHECK("loglik_final_kernel");
+    return 0;
 }
 
 extern "C" int vae_set_recon_loss(vae_ctx* c, int kind) {

@@ -119,6 +119,11 @@ struct vae_ctx {
     // reconstruction term of the ELBO (VAE_RECON_*): recon is the setting for the following forwards (vae_set_recon_loss);
     // fwd_recon is what the last forward was run with - its deferred output conv, loss and backward use that one
     int recon = VAE_RECON_BCE, fwd_recon = VAE_RECON_BCE;
+    // vae_log_likelihood: ps_part (non-null only during its decoder passes) switches the output conv to its per-sample mode
+    // (tile partials, target x[b mod ps_tb]; ps_ntile: tiles per image of the kernel taken).  ll_*: its scratch, allocated on first use.
+    double* ps_part = nullptr; int ps_tb = 0, ps_ntile = 0;
+    float* ll_f = nullptr; double* ll_part = nullptr; double* ll_lat = nullptr;   // ll_f: mu | lv | z0 [maxB*L] | z [maxB*L]
+    double* ll_kb = nullptr; size_t ll_kb_n = 0;                                   // [K*B] log p(x|z) | [K*B] log w (grown per call)
     int use_fused_wgrad = 3, knob_fused_grid = 256, use_recomp_dz = 0;   // use_fused_wgrad: bit 0 decoder (ConvT) kernels, bit 1 encoder.1 kernel
     // f16 storage: the backward runs on gradients multiplied by gmul (a power of two chosen per forward so that the stored
     // dz stay inside the f16 range: the BCE mean makes them O(1/(B*H*W))); every parameter gradient is written times ginv.
@@ -177,6 +182,8 @@ int join_comm(vae_ctx* c, hipStream_t st);
 template <typename T> int pack_weights(vae_ctx* c, const float* params, hipStream_t st);
 template <typename T> int forward_impl(vae_ctx* c, const float* x, int B, const float* params, float* bn_running, int64_t* nbt,
                                        const float* eps, uint64_t seed, int train, float* xhat, float* mu, float* lv, float* z, hipStream_t st);
+template <typename T> int encode_impl(vae_ctx* c, const float* x, int B, const float* params, float* bn_running, int64_t* nbt,
+                                      const float* eps, uint64_t seed, int train, float* mu, float* lv, float* z, hipStream_t st);
 template <typename T> int decode_impl(vae_ctx* c, const float* z, int B, const float* params, float* bn_running, int64_t* nbt, int train,
                                       const float* x, float* xhat, hipStream_t st);
 template <typename T> int backward_impl(vae_ctx* c, const float* x, const float* params, float* grads, const float* g_xhat, const float* gscale,
@@ -189,6 +196,8 @@ template <typename T> int debug_tensor_impl(vae_ctx* c, const void* src, float* 
     template int pack_weights<T>(vae_ctx*, const float*, hipStream_t);                                                                  \
     template int forward_impl<T>(vae_ctx*, const float*, int, const float*, float*, int64_t*, const float*, uint64_t, int, float*,     \
                                  float*, float*, float*, hipStream_t);                                                                  \
+    template int encode_impl<T>(vae_ctx*, const float*, int, const float*, float*, int64_t*, const float*, uint64_t, int, float*,      \
+                                float*, float*, hipStream_t);                                                                           \
     template int decode_impl<T>(vae_ctx*, const float*, int, const float*, float*, int64_t*, int, const float*, float*, hipStream_t);  \
     template int backward_impl<T>(vae_ctx*, const float*, const float*, float*, const float*, const float*, const float*, const float*, \
                                   const float*, const float*, float, int, int, hipStream_t);                                            \

@@ -442,6 +442,37 @@ static int input_bn_fwd(vae_ctx* c, int i, const float* params, float* bn_runnin
 }
 template <typename T> static bool will_pipe(vae_ctx* c, const ConvArgs<T>& a) { return c->use_pipelined && a.Cout <= c->knob_pipe_max_cout && fits_i32(a); }
 
+// Per-sample mode of the output conv (vae_log_likelihood sets c->ps_part / c->ps_tb around an eval-mode decode_impl): the
+// reconstruction term of every tile goes to c->ps_part (tile order: image, tile row, tile column; c->ps_ntile tiles per image),
+// the target of image b is x[b mod c->ps_tb]; no xhat, dlogit or accumulator is written.
+template <typename T>
+static int launch_convout_per_sample(vae_ctx* c, ConvOutArgs a, const BnFuse& f7, bool mfma_out, hipStream_t st) {
+    const int B = a.B, H = a.H;
+    const bool mse = c->fwd_recon == VAE_RECON_MSE;
+    a.part = c->ps_part; a.tB = c->ps_tb; a.xhat = nullptr; a.dlogit = nullptr; a.accum = nullptr;
+    ProfScope ps(c, "convout_fwd_per_sample", ((double)sizeof(T) * 32 + 4.0) * B * H * H, 2.0 * 9 * 32 * B * H * H, st);
+    if constexpr (sizeof(T) == 2) {
+        if (mfma_out) {
+            ConvOutFwdMfmaArgs<T> m; memset(&m, 0, sizeof(m)); m.fuse = f7; m.rev = c->knob_rev & 1;
+            m.yf = reinterpret_cast<const T*>(c->lay[7].y); m.coef = a.coef; m.wt = a.wt; m.bias = a.bias; m.target = a.target;
+            m.B = B; m.H = H; m.W = H; m.n_tiles = B * (H / 8) * (H / 32); m.inv_n = a.inv_n; m.slope = kSlope;
+            m.part = a.part; m.tB = a.tB;
+            c->ps_ntile = (H / 8) * (H / 32);
+            const dim3 grid(std::min(m.n_tiles, c->knob_convout_grid));
+            if (mse) hipLaunchKernelGGL((convout_fwd_mfma_kernel<T, VAE_RECON_MSE, true>), grid, dim3(256), 0, st, m);
+            else hipLaunchKernelGGL((convout_fwd_mfma_kernel<T, VAE_RECON_BCE, true>), grid, dim3(256), 0, st, m);
+            LAUNCH_CHECK("convout_fwd_mfma_kernel(per sample)");
+            return 0;
+        }
+    }
+    c->ps_ntile = (H / 16) * (H / 32);
+    const dim3 grid(B * (H / 16) * (H / 32));
+    if (mse) hipLaunchKernelGGL((convout_fwd_kernel<T, VAE_RECON_MSE, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((convout_fwd_kernel<T, VAE_RECON_BCE, true>), grid, dim3(256), 0, st, a);
+    LAUNCH_CHECK("convout_fwd_kernel(per sample)");
+    return 0;
+}
+
 // decoder half of the forward (models.py:147-175): decoder_input -> 3x ConvT blocks -> final_layer
 // Weight gradients are consumed only by the optimiser: with use_side_stream they run on the context's side
 // stream (own slab buffer), forked from the caller's stream at the point their inputs are ready, while the
@@ -500,6 +531,7 @@ int decode_impl(vae_ctx* c, const float* z, int B, const float* params, float* b
             c->pending_f7 = f7; c->convout_pending = 1; c->dlogit_valid = 0;
             return 0;
         }
+        if (c->ps_part) return launch_convout_per_sample<T>(c, a, f7, mfma_out, st);
         ProfScope ps(c, "convout_fwd+bce", ((double)sizeof(T) * 32 + 12.0) * B * H * H, 2.0 * 9 * 32 * B * H * H, st);
         const bool mse = c->fwd_recon == VAE_RECON_MSE;
         bool launched = false;
@@ -525,11 +557,12 @@ int decode_impl(vae_ctx* c, const float* z, int B, const float* params, float* b
     return 0;
 }
 
+// encoder half of the forward (models.py:107-145, 177-183): encoder -> fc_mu | fc_var -> mu, log_var, z = eps * std + mu
 template <typename T>
-int forward_impl(vae_ctx* c, const float* x, int B, const float* params, float* bn_running, int64_t* nbt,
-                        const float* eps, uint64_t seed, int train, float* xhat, float* mu, float* lv, float* z, hipStream_t st) {
+int encode_impl(vae_ctx* c, const float* x, int B, const float* params, float* bn_running, int64_t* nbt,
+                const float* eps, uint64_t seed, int train, float* mu, float* lv, float* z, hipStream_t st) {
     const int H = c->H, L = c->L;
-    c->B = B; c->trained = train; c->x = x; c->xhat = xhat; c->mu = mu; c->lv = lv; c->z = z;
+    c->B = B; c->trained = train; c->x = x; c->mu = mu; c->lv = lv; c->z = z;
     // f16 storage: gradient scale for the backward of this forward (vae_ctx.h): dL/dlogit is O(1/(B*H*W)), far below the
     // smallest f16 normal; 2^ceil(log2(B*H*W)) / 16 puts the stored dz around 2^-4, mid-range
     c->gmul = 1.f; c->ginv = 1.f;
@@ -595,6 +628,15 @@ int forward_impl(vae_ctx* c, const float* x, int B, const float* params, float* 
         hipLaunchKernelGGL(latent_fwd_kernel, dim3((B * L * LAT_LANES + 255) / 256), dim3(256), 0, st, la);
         LAUNCH_CHECK("latent_fwd_kernel");
     }
+    return 0;
+}
+
+template <typename T>
+int forward_impl(vae_ctx* c, const float* x, int B, const float* params, float* bn_running, int64_t* nbt,
+                        const float* eps, uint64_t seed, int train, float* xhat, float* mu, float* lv, float* z, hipStream_t st) {
+    c->xhat = xhat;
+    const int rc = encode_impl<T>(c, x, B, params, bn_running, nbt, eps, seed, train, mu, lv, z, st);
+    if (rc) return rc;
     return decode_impl<T>(c, z, B, params, bn_running, nbt, train, x, xhat, st);
 }
 

@@ -7,8 +7,13 @@ from __future__ import annotations
 import torch
 
 
-def evaluate(dataloader, model, device, partition_name="Val", verbosity=1):
+def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nll_samples=0):
+    """nll_samples = K > 0 adds ``nll`` (mean over the samples of -log p(x), importance-weighted with K draws) and ``elbo``
+    (mean per-sample ELBO), both in nats per roll (VanillaVAE.log_likelihood); 0 leaves keys, values and printout as the
+    reference has them."""
     model.eval()
+    nll_sum = torch.zeros((), device=device, dtype=torch.float64)
+    elbo_sum = torch.zeros((), device=device, dtype=torch.float64)
     n_seen = 0
     se = torch.zeros((), device=device, dtype=torch.float64)
     ae = torch.zeros((), device=device, dtype=torch.float64)
@@ -23,6 +28,10 @@ def evaluate(dataloader, model, device, partition_name="Val", verbosity=1):
                 break
         with torch.no_grad():
             output = model(stimuli)
+        if nll_samples:
+            lk = model.log_likelihood(stimuli, nll_samples)
+            nll_sum -= lk["log_likelihood"].sum()
+            elbo_sum += lk["elbo"].sum()
         rec = output["output"]
         d = (rec - stimuli).double()
         se += (d * d).sum()
@@ -39,6 +48,9 @@ def evaluate(dataloader, model, device, partition_name="Val", verbosity=1):
     results["cross-entropy"] = 0.0
     results["mse"] = 100.0 * float(se) / max(n_elem, 1)
     results["mae"] = 100.0 * float(ae) / max(n_elem, 1)
+    if nll_samples:
+        results["nll"] = float(nll_sum) / max(n_seen, 1)
+        results["elbo"] = float(elbo_sum) / max(n_seen, 1)
     if verbosity >= 1:
         print(f"\n{partition_name} evaluation results:")
         for k, v in results.items():
@@ -46,6 +58,8 @@ def evaluate(dataloader, model, device, partition_name="Val", verbosity=1):
                 print(f"  {k + ' ':.<21s}{v:7d}")
             elif "entropy" in k:
                 print(f"  {k + ' ':.<24s} {v:9.5f} nat")
+            elif k in ("nll", "elbo"):
+                print(f"  {k + ' ':.<24s} {v:9.3f} nat")
             else:
                 print(f"  {k + ' ':.<24s} {v:6.2f} %")
     return results

@@ -35,7 +35,7 @@ import torch
 from torch import Tensor, nn
 
 from . import _lib
-from .types_helpers import EncoderOutput, LossOutput, ModelOutput
+from .types_helpers import EncoderOutput, LikelihoodOutput, LossOutput, ModelOutput
 
 _DTYPES = {"f32": _lib.DTYPE_F32, "fp32": _lib.DTYPE_F32, "float32": _lib.DTYPE_F32,
            "bf16": _lib.DTYPE_BF16, "bfloat16": _lib.DTYPE_BF16,
@@ -232,6 +232,7 @@ class VanillaVAE(nn.Module):
         self.materialize_pre_latents = True
         self.eps_seed = 0
         self._fwd_count = 0
+        self._ll_count = 0      # calls of log_likelihood() that drew their noise on the device (its seeds; see there)
 
     # -- reference helpers --------------------------------------------------
     def _init_weights(self, module: nn.Sequential, name: str):
@@ -527,6 +528,55 @@ class VanillaVAE(nn.Module):
                                             self._nbt.data_ptr(), int(self.training), xhat.data_ptr(), self._stream()), "vae_decode")
         self._last = None
         return xhat
+
+    def log_likelihood(self, x: Tensor, num_samples: int = 64, *, eps: Tensor | None = None, chunk: int | None = None,
+                       seed: int | None = None) -> LikelihoodOutput:
+        """Importance-weighted estimate of log p(x) (Burda et al., IWAE with K = num_samples draws from q(z|x)) and the
+        per-sample ELBO, in nats, through the HIP kernels (include/vae_step.h: vae_log_likelihood):
+            log_weights[k, b]  = log p(x_b|z_kb) + log p(z_kb) - log q(z_kb|x_b),   z_kb ~ q(z|x_b)
+            log_likelihood[b]  = logsumexp_k log_weights[k, b] - log K
+            elbo[b]            = mean_k log p(x_b|z_kb) - KL(q(z|x_b) || N(0, I))
+        p(x|z) follows ``recon_loss``: "bce" - Bernoulli (normalised only for 0/1 targets), "mse" - Gaussian with variance
+        1/2, whose negative log-likelihood is the summed squared error plus (H*W/2) log(pi).
+
+        Always in eval semantics (BatchNorm on the running statistics, which are read and never written), whatever
+        ``self.training`` is; not differentiable.  The training noise seeds are untouched.  ``eps`` [K, B, latent_dim]
+        replaces the draws; by default they come from the device generator with ``seed`` (None: derived from ``eps_seed``
+        and a call counter of this method).  ``chunk`` draws of the whole batch are decoded per pass (default: as many as
+        the model's max_batch allows)."""
+        K = int(num_samples)
+        if K < 1:
+            raise ValueError(f"num_samples must be >= 1, got {num_samples}")
+        if chunk is not None and int(chunk) < 1:
+            raise ValueError(f"chunk must be >= 1, got {chunk}")
+        B, L = (x.shape[0] if x.dim() else 0), self.latent_dim
+        if eps is not None and tuple(eps.shape) != (K, B, L):
+            raise ValueError(f"eps must be [{K},{B},{L}] (num_samples, batch, latent_dim), got {tuple(eps.shape)}")
+        self._check_input(x)
+        x = x.detach().contiguous().float()
+        dev = x.device
+        ctx = self._context(B)
+        if chunk is None:
+            chunk = max(1, min(K, ctx.key[2] // B))
+        else:
+            chunk = min(int(chunk), K)
+            if chunk * B > ctx.key[2]:
+                ctx = self._context(chunk * B)
+        if eps is not None:
+            eps = eps.detach().to(dev, torch.float32).contiguous()
+        if seed is None:
+            self._ll_count = getattr(self, "_ll_count", 0) + 1
+            seed = int(self.eps_seed) + self._ll_count + _rank() * 0x9E3779B97F4A7C15
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        log_w = torch.empty(K, B, device=dev, dtype=torch.float64)
+        ll = torch.empty(B, device=dev, dtype=torch.float64)
+        elbo = torch.empty(B, device=dev, dtype=torch.float64)
+        with self._device_guard():
+            _lib.check(_lib.lib().vae_log_likelihood(
+                ctx.handle, x.data_ptr(), B, self._flat.data_ptr(), self._bnflat.data_ptr(), K, chunk, _lib.ptr(eps), seed,
+                log_w.data_ptr(), ll.data_ptr(), elbo.data_ptr(), self._stream()), "vae_log_likelihood")
+        self._last = None
+        return LikelihoodOutput(log_likelihood=ll, elbo=elbo, log_weights=log_w)
 
     def reparameterize(self, mu: Tensor, log_var: Tensor) -> Tensor:
         """models.py:177-183 (plumbing-level torch ops; the hot path fuses this into the latent kernel)."""

@@ -21,3 +21,9 @@ class LossOutput(TypedDict):
     loss: Tensor
     reconstruction_loss: Tensor
     kld_loss: Tensor
+
+
+class LikelihoodOutput(TypedDict):
+    log_likelihood: Tensor    # [B] float64: importance-weighted estimate of log p(x) (nats)
+    elbo: Tensor              # [B] float64: per-sample evidence lower bound (nats)
+    log_weights: Tensor       # [K, B] float64: log p(x|z_k) + log p(z_k) - log q(z_k|x)
