@@ -80,9 +80,17 @@ int vae_forward(vae_ctx* ctx, const float* x, int batch, const float* params, fl
                 float* mu, float* log_var, float* z, vae_stream_t stream);
 
 /* VanillaVAE.decode (models.py:147-175): z [B,L] -> xhat [B,1,H,W].  train!=0 uses (and updates) batch
- * statistics like a train-mode module call; the pass is not differentiable (vae_backward needs vae_forward). */
+ * statistics like a train-mode module call.  Differentiable through vae_backward_ex (not vae_backward); z and xhat
+ * must stay valid until that backward has run. */
 int vae_decode(vae_ctx* ctx, const float* z, int batch, const float* params, float* bn_running,
                int64_t* num_batches_tracked, int train, float* xhat, vae_stream_t stream);
+
+/* VanillaVAE.encode (models.py:107-145) and the reparameterisation, without the decoder: the same launches as the
+ * encoder half of vae_forward, so mu / log_var are bit-identical to its outputs for the same input, parameters and
+ * train value.  Arguments as vae_forward.  Differentiable through vae_backward_ex (not vae_backward). */
+int vae_encode(vae_ctx* ctx, const float* x, int batch, const float* params, float* bn_running,
+               int64_t* num_batches_tracked, const float* eps, uint64_t seed, int train, float* mu,
+               float* log_var, float* z, vae_stream_t stream);
 
 /* EncoderOutput.pre_latents (models.py:133, types_helpers.py:20) of the last forward,
  * [B, flattened_size] f32 in the reference's NCHW-flatten order. */
@@ -152,6 +160,17 @@ int vae_backward(vae_ctx* ctx, const float* x, const float* params, float* grads
 int vae_backward_part(vae_ctx* ctx, const float* x, const float* params, float* grads, const float* g_xhat,
                  const float* gscale, const float* g_mu, const float* g_log_var, const float* g_z,
                  const float* g_pre, float kld_weight, int use_std, int part, vae_stream_t stream);
+/* The backward of whichever forward ran last on the context: vae_forward (train or eval mode), vae_encode or
+ * vae_decode.  Arguments as vae_backward, plus:
+ *   dx [B,1,H,W]: dL/dx of a vae_forward / vae_encode input, written when not NULL (else never computed)
+ *   dz [B,L]:     dL/dz of a vae_decode input, written when not NULL
+ * After an eval-mode forward BatchNorm is differentiated on the running statistics (which are not written).
+ * vae_encode: only g_mu / g_log_var / g_pre apply (use_std must be 0, g_xhat and g_z NULL); the decoder's gradients
+ * in `grads` are left as they were.  vae_decode: only g_xhat applies (use_std must be 0: there is no target; x may be
+ * NULL); the encoder, fc_mu and fc_var gradients in `grads` are left as they were. */
+int vae_backward_ex(vae_ctx* ctx, const float* x, const float* params, float* grads, const float* g_xhat,
+                    const float* gscale, const float* g_mu, const float* g_log_var, const float* g_z,
+                    const float* g_pre, float kld_weight, int use_std, float* dx, float* dz, vae_stream_t stream);
 /* A non-blocking stream owned by the context, ordered after everything enqueued on `stream` so far.  Data-parallel
  * callers enqueue the decoder bucket's all-reduce on it right after part 1; it is joined back into the caller's
  * stream at the end of part 2, so the collective overlaps the encoder half without any host-side handshake. */

@@ -377,12 +377,32 @@ extern "C" int vae_decode(vae_ctx* c, const float* z, int B, const float* params
     if (B < 1 || B > c->maxB) return vae_set_error("vae_decode", "batch exceeds the context's max_batch");
     if (!z || !params || !xhat) return vae_set_error("vae_decode", "null tensor pointer");
     hipStream_t st = (hipStream_t)stream;
-    c->B = B; c->trained = 0; c->fwd_recon = c->recon;   // a decode-only pass cannot be differentiated
+    c->cur_stream = st; c->cur_stream_set = true;
+    // what vae_backward_ex needs of a decode-only pass (its BatchNorm mode, z, xhat, the gradient scale); vae_backward refuses it
+    c->B = B; c->trained = train; c->fwd_kind = 2; c->fwd_recon = c->recon;   // (c->B: the batch statistics' count)
+    c->x = xhat; c->xhat = xhat; c->z = const_cast<float*>(z); c->mu = c->lv = nullptr;
+    set_grad_scale(c, B);
     HIP_CHECK_RET(hipMemsetAsync(c->dstats, 0, c->n_dstats * sizeof(double), st)); c->bwd_dirty = 0;
     int rc = VAE_DISPATCH(c->dtype, pack_weights, (c, params, st));
-    if (rc) return rc;
+    if (rc) { c->B = 0; return rc; }
     // the reconstruction-loss side outputs of the output-conv kernel are unused here: xhat doubles as the target
-    return VAE_DISPATCH(c->dtype, decode_impl, (c, z, B, params, bn_running, nbt, train, xhat, xhat, st));
+    rc = VAE_DISPATCH(c->dtype, decode_impl, (c, z, B, params, bn_running, nbt, train, xhat, xhat, st));
+    if (rc) c->B = 0;
+    return rc;
+}
+
+extern "C" int vae_encode(vae_ctx* c, const float* x, int B, const float* params, float* bn_running, int64_t* nbt,
+                          const float* eps, uint64_t seed, int train, float* mu, float* lv, float* z, vae_stream_t stream) {
+    if (!c) return vae_set_error("vae_encode", "null ctx");
+    if (B < 1 || B > c->maxB) return vae_set_error("vae_encode", "batch exceeds the context's max_batch");
+    if (!x || !params || !mu || !lv || !z) return vae_set_error("vae_encode", "null tensor pointer");
+    hipStream_t st = (hipStream_t)stream;
+    c->cur_stream = st; c->cur_stream_set = true;
+    c->fwd_recon = c->recon; c->xhat = nullptr; c->dlogit_valid = 0; c->convout_pending = 0;
+    c->fwd_kind = 1;
+    const int rc = VAE_DISPATCH(c->dtype, encode_impl, (c, x, B, params, bn_running, nbt, eps, seed, train, mu, lv, z, st));
+    if (rc) c->B = 0;
+    return rc;
 }
 
 // Importance-weighted log-likelihood and per-sample ELBO (loglik.cuh).  One eval-mode encoder pass; then per chunk of draws
@@ -467,7 +487,7 @@ extern "C" int vae_loss(vae_ctx* c, float kld_weight, float* out3, vae_stream_t 
 // on this context - for callers that only read the ELBO after the backward (train.py:644-674 reads it after the step).
 extern "C" int vae_loss_deferred(vae_ctx* c, float kld_weight, float* out3, vae_stream_t stream) {
     if (!c || !c->B) return vae_set_error("vae_loss_deferred", "no forward");
-    if (!c->trained) return vae_set_error("vae_loss_deferred", "needs a train-mode forward (a backward must follow)");
+    if (!c->trained || c->fwd_kind) return vae_set_error("vae_loss_deferred", "needs a train-mode forward (a backward must follow)");
     if (c->convout_pending) { c->loss_out3 = out3; c->loss_kw = kld_weight; return 0; }   // finalised by the backward, after the fused output-conv kernel
     SideFork f = (c->knob_lean & 4) ? fork_side(c, (hipStream_t)stream) : SideFork{(hipStream_t)stream, c->slab, 0};
     if (f.rc) return f.rc;
@@ -532,6 +552,15 @@ extern "C" int vae_backward_part(vae_ctx* c, const float* x, const float* params
     hipStream_t st = (hipStream_t)stream;
     c->cur_stream = st; c->cur_stream_set = true;
     return VAE_DISPATCH(c->dtype, backward_impl, (c, x, params, grads, g_xhat, gscale, g_mu, g_lv, g_z, g_pre, kld_weight, add_kl, part, st));
+}
+extern "C" int vae_backward_ex(vae_ctx* c, const float* x, const float* params, float* grads, const float* g_xhat, const float* gscale,
+                               const float* g_mu, const float* g_lv, const float* g_z, const float* g_pre, float kld_weight, int add_kl,
+                               float* dx, float* dz, vae_stream_t stream) {
+    if (!c) return vae_set_error("vae_backward_ex", "null ctx");
+    if (!params || !grads || (!x && c->fwd_kind != 2)) return vae_set_error("vae_backward_ex", "null tensor pointer");
+    hipStream_t st = (hipStream_t)stream;
+    c->cur_stream = st; c->cur_stream_set = true;
+    return VAE_DISPATCH(c->dtype, backward_ex_impl, (c, x, params, grads, g_xhat, gscale, g_mu, g_lv, g_z, g_pre, kld_weight, add_kl, dx, dz, st));
 }
 extern "C" int vae_backward(vae_ctx* c, const float* x, const float* params, float* grads, const float* g_xhat, const float* gscale,
                             const float* g_mu, const float* g_lv, const float* g_z, const float* g_pre, float kld_weight, int add_kl,

@@ -129,8 +129,9 @@ struct vae_ctx {
     // dz stay inside the f16 range: the BCE mean makes them O(1/(B*H*W))); every parameter gradient is written times ginv.
     // The backward is linear in the upstream gradient, so this changes no f32 result (powers of two are exact).  1 otherwise.
     float gmul, ginv;
-    // last forward
-    int B; int trained; const float* x; float *xhat, *mu, *lv, *z;
+    // last forward; fwd_kind: what it ran - 0 the whole model (vae_forward, the training steps), 1 the encoder only (vae_encode),
+    // 2 the decoder only (vae_decode); vae_backward_ex differentiates whichever it was
+    int B; int trained; int fwd_kind = 0; const float* x; float *xhat, *mu, *lv, *z;
     int use_tr16, use_mfma_convout, use_pipelined, knob_up_per_cu, knob_convout_grid, knob_convout_bwd_grid, knob_down_per_cu, knob_nt_max, knob_pipe_max_cout, knob_ablate_b; long long* dbg_buf; char dbg_tag[32]; int dbg_epi; int64_t ws_bytes;
     std::vector<void*> allocs;
     // per-kernel timing (bench.py roofline): HIP events on the launch stream
@@ -172,6 +173,16 @@ static inline size_t wgrad_slab_floats(const WgradKnobs& k, int B, int Hs, int W
     return per * nsplit;
 }
 
+// f16 storage: the gradient scale of a backward over B images (gmul / ginv above); 1 for the other storage types
+static inline void set_grad_scale(vae_ctx* c, int B) {
+    // dL/dlogit is O(1/(B*H*W)), far below the smallest f16 normal; 2^ceil(log2(B*H*W)) / 16 puts the stored dz around 2^-4, mid-range
+    c->gmul = 1.f; c->ginv = 1.f;
+    if (c->dtype == VAE_DTYPE_F16) {
+        const int e = std::max(0, ilog2(B) + 2 * ilog2(c->H) - 4);
+        c->gmul = ldexpf(1.f, e); c->ginv = ldexpf(1.f, -e);
+    }
+}
+
 // side streams (vae_api.hip)
 struct SideFork { hipStream_t st; float* slab; int rc; };
 SideFork fork_side(vae_ctx* c, hipStream_t st, int which = -1);
@@ -189,6 +200,9 @@ template <typename T> int decode_impl(vae_ctx* c, const float* z, int B, const f
 template <typename T> int backward_impl(vae_ctx* c, const float* x, const float* params, float* grads, const float* g_xhat, const float* gscale,
                                         const float* g_mu, const float* g_lv, const float* g_z, const float* g_pre, float kld_weight, int add_kl,
                                         int part, hipStream_t st);
+template <typename T> int backward_ex_impl(vae_ctx* c, const float* x, const float* params, float* grads, const float* g_xhat, const float* gscale,
+                                           const float* g_mu, const float* g_lv, const float* g_z, const float* g_pre, float kld_weight, int add_kl,
+                                           float* dx, float* dz, hipStream_t st);
 template <typename T> int pre_latents_impl(vae_ctx* c, float* out, hipStream_t st);
 template <typename T> int debug_tensor_impl(vae_ctx* c, const void* src, float* out, long n, int C, int HW, hipStream_t st);
 
@@ -201,6 +215,8 @@ template <typename T> int debug_tensor_impl(vae_ctx* c, const void* src, float* 
     template int decode_impl<T>(vae_ctx*, const float*, int, const float*, float*, int64_t*, int, const float*, float*, hipStream_t);  \
     template int backward_impl<T>(vae_ctx*, const float*, const float*, float*, const float*, const float*, const float*, const float*, \
                                   const float*, const float*, float, int, int, hipStream_t);                                            \
+    template int backward_ex_impl<T>(vae_ctx*, const float*, const float*, float*, const float*, const float*, const float*, const float*, \
+                                     const float*, const float*, float, int, float*, float*, hipStream_t);                               \
     template int pre_latents_impl<T>(vae_ctx*, float*, hipStream_t);                                                                    \
     template int debug_tensor_impl<T>(vae_ctx*, const void*, float*, long, int, int, hipStream_t);
 

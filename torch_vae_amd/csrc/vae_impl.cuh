@@ -12,6 +12,7 @@
 #include "wgrad_split.cuh"
 #include "upfinal_stream.cuh"
 #include "dnfirst_stream.cuh"
+#include "grad_paths.cuh"
 
 // ---------------------------------------------------------------------------
 template <typename K> static int set_lds(K kernel, size_t bytes) {
@@ -422,6 +423,18 @@ static int bn_finalize_now(vae_ctx* c, const BnFuse& f, hipStream_t st) {
     LAUNCH_CHECK("bn_finalize_kernel");
     return 0;
 }
+// Backward finalisation of a BN layer as its own launch; the consumers then read p0..p2 from the block (mode BNF_NONE).  After an
+// eval-mode forward always: BatchNorm on the running statistics (bn_eval_bwd_kernel, grad_paths.cuh).
+static int bn_bwd_standalone(vae_ctx* c, BnFuse& f, hipStream_t st) {
+    if (c->trained) { if (bn_finalize_now(c, f, st)) return -1; }
+    else {
+        ProfScope ps(c, "bn_eval_bwd_finalize", 0, 0, st);
+        hipLaunchKernelGGL(bn_eval_bwd_kernel, dim3(1), dim3(256), 0, st, f);
+        LAUNCH_CHECK("bn_eval_bwd_kernel");
+    }
+    f.mode = BNF_NONE;
+    return 0;
+}
 // Coefficients of layer i for the kernel that stages its tensor next.  Train mode with a fusing consumer: returns
 // the BnFuse descriptor (mode BNF_FWD) and launches nothing; otherwise the block is filled by a standalone launch
 // (batch statistics, or running statistics in eval mode) and the returned descriptor has mode BNF_NONE.
@@ -563,13 +576,7 @@ int encode_impl(vae_ctx* c, const float* x, int B, const float* params, float* b
                 const float* eps, uint64_t seed, int train, float* mu, float* lv, float* z, hipStream_t st) {
     const int H = c->H, L = c->L;
     c->B = B; c->trained = train; c->x = x; c->mu = mu; c->lv = lv; c->z = z;
-    // f16 storage: gradient scale for the backward of this forward (vae_ctx.h): dL/dlogit is O(1/(B*H*W)), far below the
-    // smallest f16 normal; 2^ceil(log2(B*H*W)) / 16 puts the stored dz around 2^-4, mid-range
-    c->gmul = 1.f; c->ginv = 1.f;
-    if (c->dtype == VAE_DTYPE_F16) {
-        const int e = std::max(0, ilog2(B) + 2 * ilog2(H) - 4);
-        c->gmul = ldexpf(1.f, e); c->ginv = ldexpf(1.f, -e);
-    }
+    set_grad_scale(c, B);   // f16 storage: gradient scale for the backward of this forward (vae_ctx.h)
     HIP_CHECK_RET(hipMemsetAsync(c->dstats, 0, c->n_dstats * sizeof(double), st)); c->bwd_dirty = 0; c->walk_dir = 1;
     static const char* kLayerTag[8] = {"encoder.0", "encoder.1", "encoder.2", "encoder.3", "decoder.0", "decoder.1", "decoder.2", "final_layer.0"};
     // encoder block 0 (reads the raw f32 weights); the MFMA layers' packed weight images are built meanwhile
@@ -634,7 +641,7 @@ int encode_impl(vae_ctx* c, const float* x, int B, const float* params, float* b
 template <typename T>
 int forward_impl(vae_ctx* c, const float* x, int B, const float* params, float* bn_running, int64_t* nbt,
                         const float* eps, uint64_t seed, int train, float* xhat, float* mu, float* lv, float* z, hipStream_t st) {
-    c->xhat = xhat;
+    c->xhat = xhat; c->fwd_kind = 0;
     const int rc = encode_impl<T>(c, x, B, params, bn_running, nbt, eps, seed, train, mu, lv, z, st);
     if (rc) return rc;
     return decode_impl<T>(c, z, B, params, bn_running, nbt, train, x, xhat, st);
@@ -667,7 +674,7 @@ static int launch_convt_fused(vae_ctx* c, int i, const float* params, float* gra
         ConvTFusedArgs<T> a; memset(&a, 0, sizeof(a));
         a.dz = reinterpret_cast<const T*>(l.dz); a.y = reinterpret_cast<const T*>(l.y); a.gcoef = l.block + LC_P0 * l.C;
         a.fuse = make_fuse_bwd(c, i, params, grads);
-        if (!c->use_fused_bn) { if (bn_finalize_now(c, a.fuse, st)) return -1; a.fuse.mode = BNF_NONE; }   // standalone finalisation: coefficients from the block
+        if (!c->use_fused_bn || !c->trained) { if (bn_bwd_standalone(c, a.fuse, st)) return -1; }   // standalone finalisation: coefficients from the block
         a.wp = reinterpret_cast<const T*>(c->wp_dg[i]);
         a.yprev = reinterpret_cast<const T*>(lp.y); a.ocoef = lp.block; a.dzprev = reinterpret_cast<T*>(lp.dz); a.stat = lp.stat_b;
         a.slab = c->fused_slab[fs]; a.slope = kSlope;
@@ -711,7 +718,7 @@ static int launch_conv_fused(vae_ctx* c, int i, const float* params, float* grad
         if ((size_t)grid * 9 * 64 * 32 > c->fused_slab_floats) return 1;
         a.dz = reinterpret_cast<const T*>(l.dz); a.y = reinterpret_cast<const T*>(l.y); a.gcoef = l.block + LC_P0 * l.C;
         a.fuse = make_fuse_bwd(c, i, params, grads);
-        if (!c->use_fused_bn) { if (bn_finalize_now(c, a.fuse, st)) return -1; a.fuse.mode = BNF_NONE; }
+        if (!c->use_fused_bn || !c->trained) { if (bn_bwd_standalone(c, a.fuse, st)) return -1; }
         a.wp = reinterpret_cast<const T*>(c->wp_dg[i]);
         a.yprev = reinterpret_cast<const T*>(lp.y); a.ocoef = lp.block; a.dzprev = reinterpret_cast<T*>(lp.dz); a.stat = lp.stat_b;
         a.slab = c->fused_slab[2]; a.slope = kSlope; a.B = c->B; a.Hs = Hs; a.Ws = Ws; a.rev = (c->knob_rev >> 2) & 1; a.ablate = c->knob_ablate_f;
@@ -743,12 +750,7 @@ static bool raw_wgrad_ok(vae_ctx* c, int i) {
     return sizeof(T) == 2 && c->use_raw_wgrad && c->use_pipelined && c->wk.wide && c->wk.tile == 1 && !c->wk.force_simple && i >= 2 && i <= 5;
 }
 
-template <typename T>
-static int backward_first(vae_ctx* c, const float* x, const float* params, float* grads, const float* g_xhat, const float* gscale,
-                         const float* g_mu, const float* g_lv, const float* g_z, const float* g_pre, float kld_weight, int add_kl,
-                         hipStream_t st) {
-    if (!c->B || !c->trained) return vae_set_error("vae_backward", "no train-mode forward to differentiate");
-    const int B = c->B, H = c->H, L = c->L;
+static int bwd_clear_stats(vae_ctx* c, hipStream_t st) {
     size_t nfwd = 0;
     for (int i = 0; i < 8; ++i) nfwd += 2 * kBnC[i] * STAT_R;
     if (c->bwd_dirty) {   // (the forward zeroed every accumulator; only a repeated backward has to clear its own)
@@ -756,6 +758,17 @@ static int backward_first(vae_ctx* c, const float* x, const float* params, float
         for (int rep = 0; rep < STAT_R; ++rep) HIP_CHECK_RET(hipMemsetAsync(c->accum + rep * 8 + 2, 0, sizeof(double), st));
     }
     c->bwd_dirty = 1;
+    return 0;
+}
+
+// ex: called by vae_backward_ex, which also differentiates eval-mode and decode-only forwards
+template <typename T>
+static int backward_first(vae_ctx* c, const float* x, const float* params, float* grads, const float* g_xhat, const float* gscale,
+                         const float* g_mu, const float* g_lv, const float* g_z, const float* g_pre, float kld_weight, int add_kl,
+                         hipStream_t st, bool ex = false) {
+    if (!c->B || !(c->trained || ex)) return vae_set_error("vae_backward", "no train-mode forward to differentiate");
+    const int B = c->B, H = c->H, L = c->L;
+    if (bwd_clear_stats(c, st)) return -1;
     const float* dl_src = c->dlogit; const float* dl_scale = gscale;
     const bool step7 = c->convout_pending != 0;
     if (step7 && (g_xhat || gscale || !add_kl)) return vae_set_error("vae_backward", "the forward ran with train = 2: only the standard ELBO backward (no upstream gradient on xhat, no loss scale) can follow");
@@ -891,7 +904,7 @@ static int backward_first(vae_ctx* c, const float* x, const float* params, float
         }
         // BatchNorm backward of this layer: folded into both consumers (the input-gradient kernel records it)
         BnFuse fb = make_fuse_bwd(c, i, params, grads);
-        if (!(c->use_fused_bn && will_pipe(c, a))) { if (bn_finalize_now(c, fb, st)) return -1; fb.mode = BNF_NONE; }
+        if (!(c->use_fused_bn && will_pipe(c, a)) || !c->trained) { if (bn_bwd_standalone(c, fb, st)) return -1; }
         w.fuse = fb; a.fuse = fb;
         // deep layers: the input-gradient kernel materialises g = BN-backward(dz, y) while staging it; the weight gradient then
         // reads g and the forward's materialised activation as plain copies (it must follow the input-gradient launch)
@@ -911,17 +924,21 @@ static int backward_first(vae_ctx* c, const float* x, const float* params, float
 }
 
 // second half of the backward: decoder_input / latent / fc / encoder (everything below the decoder stack)
+// mode 0: everything below the decoder stack; 1 (encoder-only forward): no decoder_input backward, the latent gradient starts at the
+// upstream g_mu / g_lv / g_pre; 2 (decoder-only forward): decoder_input backward only, ending with dL/dz written to `out` [B,L].
+// Modes 0 and 1 write dL/dx to `out` [B,1,H,W] when it is not null (conv1_dgrad_kernel, after encoder.0's weight gradient).
 template <typename T>
 static int backward_second(vae_ctx* c, const float* x, const float* params, float* grads, const float* gscale,
                            const float* g_mu, const float* g_lv, const float* g_z, const float* g_pre, float kld_weight, int add_kl,
-                           hipStream_t st) {
+                           hipStream_t st, int mode = 0, float* out = nullptr) {
     const int B = c->B, H = c->H, L = c->L;
     static const char* kLayerTag[8] = {"encoder.0", "encoder.1", "encoder.2", "encoder.3", "decoder.0", "decoder.1", "decoder.2", "final_layer.0"};
     // decoder_input backward, reparameterisation + KL backward
     c->tag = "latent";
     {
         const bool lat_mfma = (c->use_latent_mfma & 4) && 2 * L <= 9 * 32;   // fc weight gradient path (also produces the bias column sums)
-        if ((c->use_latent_mfma & 2) && L + 1 <= 9 * 32) {   // weight + bias gradient in one launch, no slabs (latent_mfma.cuh)
+        if (mode == 1) {}
+        else if ((c->use_latent_mfma & 2) && L + 1 <= 9 * 32) {   // weight + bias gradient in one launch, no slabs (latent_mfma.cuh)
             SideFork f = fork_side(c, st);
             if (f.rc) return f.rc;
             BatchGemmArgs g; memset(&g, 0, sizeof(g));
@@ -947,11 +964,20 @@ static int backward_second(vae_ctx* c, const float* x, const float* params, floa
             if (launch_reduce(sw, nz, (size_t)c->F * L, grads + c->poff[20], 0, 0, f.st, c)) return -1;
             if (launch_reduce(sb, nz, (size_t)c->F, grads + c->poff[21], 0, 0, f.st, c)) return -1;
         }
-        DenseArgs<T> a; memset(&a, 0, sizeof(a));
-        a.A = reinterpret_cast<const T*>(c->dd0); a.coef = nullptr; a.slope = 1.f; a.C = 256;
-        a.Bp = reinterpret_cast<const T*>(c->dipack); a.M = B; a.K = (int)c->F; a.Npad = c->npad_di;
-        int nsplit;
-        if (launch_dense<T>(c, a, &nsplit, st)) return -1;
+        int nsplit = 0;
+        if (mode == 0 || (mode == 2 && out)) {
+            DenseArgs<T> a; memset(&a, 0, sizeof(a));
+            a.A = reinterpret_cast<const T*>(c->dd0); a.coef = nullptr; a.slope = 1.f; a.C = 256;
+            a.Bp = reinterpret_cast<const T*>(c->dipack); a.M = B; a.K = (int)c->F; a.Npad = c->npad_di;
+            if (launch_dense<T>(c, a, &nsplit, st)) return -1;
+        }
+        if (mode == 2) {
+            if (!out) return join_sides(c, st);
+            ProfScope ps(c, "latent_dz", 4.0 * nsplit * B * L + 4.0 * B * L, 0, st);
+            hipLaunchKernelGGL(latent_dz_kernel, dim3((B * L + 255) / 256), dim3(256), 0, st, c->slab, nsplit, c->npad_di, B, L, c->ginv, out);
+            LAUNCH_CHECK("latent_dz_kernel");
+            return join_sides(c, st);
+        }
         LatentBwdArgs lb;
         lb.slab = c->slab; lb.nslab = nsplit; lb.npad = c->npad_di; lb.mu = c->mu; lb.lv = c->lv; lb.eps = c->eps; lb.gscale = gscale;
         lb.gmu = g_mu; lb.glv = g_lv; lb.gz = g_z; lb.dlat = c->dlat; lb.B = B; lb.L = L; lb.kld_weight = kld_weight; lb.add_kl = add_kl; lb.gmul = c->gmul;
@@ -1050,7 +1076,7 @@ static int backward_second(vae_ctx* c, const float* x, const float* params, floa
         a.out = reinterpret_cast<T*>(lp.dz); a.yout = reinterpret_cast<const T*>(lp.y); a.ocoef = lp.block; a.oslope = kSlope; a.stat = lp.stat_b; a.epi = EPI_BWD;
         a.B = B; a.Hs = l.H; a.Ws = l.W; a.Cin = l.C; a.Cout = lp.C;
         BnFuse fb = make_fuse_bwd(c, i, params, grads);
-        if (!(c->use_fused_bn && will_pipe(c, a))) { if (bn_finalize_now(c, fb, st)) return -1; fb.mode = BNF_NONE; }
+        if (!(c->use_fused_bn && will_pipe(c, a)) || !c->trained) { if (bn_bwd_standalone(c, fb, st)) return -1; }
         w.fuse = fb; a.fuse = fb;
         const bool raw = raw_wgrad_ok<T>(c, i) && l.dy && will_pipe(c, a) && lp.act_ok;
         if (raw) {   // (as in the decoder loop)
@@ -1067,7 +1093,7 @@ static int backward_second(vae_ctx* c, const float* x, const float* params, floa
     {
         c->tag = kLayerTag[0];
         BnFuse fb0 = make_fuse_bwd(c, 0, params, grads);
-        if (!c->use_fused_bn || !(c->knob_lean & 2)) { if (bn_finalize_now(c, fb0, st)) return -1; fb0.mode = BNF_NONE; }
+        if (!c->use_fused_bn || !(c->knob_lean & 2) || !c->trained) { if (bn_bwd_standalone(c, fb0, st)) return -1; }
         const long P = (long)B * (H / 2) * (H / 2);
         const int grid = (int)std::min<long>((P / 4 + 63) / 64, 512);   // (a thread takes quads of 4 output pixels)
         // last link of the chain: stays on the caller's stream (a side stream would only add an event round trip)
@@ -1079,6 +1105,14 @@ static int backward_second(vae_ctx* c, const float* x, const float* params, floa
             LAUNCH_CHECK("conv1_wgrad_kernel");
         }
         if (launch_reduce(f.slab, grid, 288, grads + c->poff[0], 32, 1, f.st, c)) return -1;
+        if (out) {   // input gradient: reads the p0..p2 the weight-gradient launch above finalised into the block
+            if (P >= (1L << 31)) return vae_set_error("vae_backward_ex", "input gradient: batch too large for 32-bit pixel indices");
+            const long Q = (P + 63) / 64;
+            ProfScope ps(c, "conv1_dgrad", (double)sizeof(T) * 64.0 * P + 4.0 * B * H * H, 2.0 * 9 * 32 * P, st);
+            hipLaunchKernelGGL((conv1_dgrad_kernel<T>), dim3((unsigned)std::min<long>(Q, 2048)), dim3(256), 0, st, reinterpret_cast<const T*>(c->lay[0].dz),
+                               reinterpret_cast<const T*>(c->lay[0].y), c->lay[0].block + LC_P0 * 32, params + c->poff[0], out, B, H, H, c->ginv);
+            LAUNCH_CHECK("conv1_dgrad_kernel");
+        }
     }
     return join_sides(c, st);
 }
@@ -1090,6 +1124,7 @@ int backward_impl(vae_ctx* c, const float* x, const float* params, float* grads,
                          const float* g_mu, const float* g_lv, const float* g_z, const float* g_pre, float kld_weight, int add_kl,
                          int part, hipStream_t st) {
     if (part < 0 || part > 2) return vae_set_error("vae_backward", "part must be 0, 1 or 2");
+    if (c->fwd_kind != 0 && c->B) return vae_set_error("vae_backward", "the last forward ran the encoder or the decoder only: use vae_backward_ex");
     if (part != 2) {
         if (backward_first<T>(c, x, params, grads, g_xhat, gscale, g_mu, g_lv, g_z, g_pre, kld_weight, add_kl, st)) return -1;
         c->bwd_half_done = 1;
@@ -1097,6 +1132,31 @@ int backward_impl(vae_ctx* c, const float* x, const float* params, float* grads,
     } else if (!c->bwd_half_done) return vae_set_error("vae_backward", "part 2 before part 1");
     c->bwd_half_done = 0;
     if (backward_second<T>(c, x, params, grads, gscale, g_mu, g_lv, g_z, g_pre, kld_weight, add_kl, st)) return -1;
+    return join_comm(c, st);
+}
+
+// vae_backward_ex: differentiates the last forward of whichever kind (c->fwd_kind), train or eval mode
+template <typename T>
+int backward_ex_impl(vae_ctx* c, const float* x, const float* params, float* grads, const float* g_xhat, const float* gscale,
+                     const float* g_mu, const float* g_lv, const float* g_z, const float* g_pre, float kld_weight, int add_kl,
+                     float* dx, float* dz, hipStream_t st) {
+    if (!c->B) return vae_set_error("vae_backward_ex", "no forward to differentiate");
+    if (c->fwd_kind == 2) {
+        if (add_kl) return vae_set_error("vae_backward_ex", "the last forward was decode-only: it has no target, so there is no standard ELBO (use_std must be 0)");
+        if (g_mu || g_lv || g_z || g_pre || dx) return vae_set_error("vae_backward_ex", "the last forward was decode-only: only g_xhat and dz apply");
+        if (backward_first<T>(c, x, params, grads, g_xhat, nullptr, nullptr, nullptr, nullptr, nullptr, kld_weight, 0, st, true)) return -1;
+        if (backward_second<T>(c, x, params, grads, nullptr, nullptr, nullptr, nullptr, nullptr, kld_weight, 0, st, 2, dz)) return -1;
+        return join_comm(c, st);
+    }
+    if (dz) return vae_set_error("vae_backward_ex", "dz is the input gradient of a decode-only forward");
+    if (c->fwd_kind == 1) {
+        if (add_kl || g_xhat) return vae_set_error("vae_backward_ex", "the last forward was encode-only: there is no reconstruction (no g_xhat, use_std must be 0)");
+        if (bwd_clear_stats(c, st)) return -1;
+        if (backward_second<T>(c, x, params, grads, nullptr, g_mu, g_lv, nullptr, g_pre, kld_weight, 0, st, 1, dx)) return -1;
+        return join_comm(c, st);
+    }
+    if (backward_first<T>(c, x, params, grads, g_xhat, gscale, g_mu, g_lv, g_z, g_pre, kld_weight, add_kl, st, true)) return -1;
+    if (backward_second<T>(c, x, params, grads, gscale, g_mu, g_lv, g_z, g_pre, kld_weight, add_kl, st, 0, dx)) return -1;
     return join_comm(c, st);
 }
 

@@ -19,6 +19,8 @@ Deviations from the reference, all explicit:
     256*(input_dim/16)^2 instead of the hard-wired 1024 (models.py:33,166).
   * gradients are written to ``param.grad`` by the backward kernel directly
     (no AccumulateGrad hooks fire).
+  * ``decode(z)`` records an autograd graph only when ``z`` requires grad (the reference's does whenever a decoder
+    parameter requires grad); ``sample()`` runs under ``torch.no_grad()``.
   * ``recon_loss="mse"`` (keyword-only; default ``"bce"``, the reference's
     models.py:208) replaces the reconstruction term of the ELBO by
     ``F.mse_loss(xhat, x)`` - a Gaussian likelihood for velocity-valued rolls
@@ -102,14 +104,59 @@ class _VAEForward(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_xhat, g_mu, g_lv, g_z, g_pre, g_handle):
-        model = ctx.model_ref()
-        if model is None:
-            raise RuntimeError("the VanillaVAE of this graph no longer exists")
-        if model._fwd_count != ctx.generation:
-            raise RuntimeError("backward through a forward that is no longer the model's last one: the context keeps the "
-                               "activations of one forward only (run backward before the next forward, or one model per graph)")
-        model._run_backward(g_xhat, g_mu, g_lv, g_z, g_pre, g_handle)
-        return None, None, None, None
+        model = _graph_model(ctx)
+        if model._last["train"] and not ctx.needs_input_grad[0]:
+            model._run_backward(g_xhat, g_mu, g_lv, g_z, g_pre, g_handle)     # the training path: vae_backward, as always
+            return None, None, None, None
+        dx, _ = model._run_backward_ex(g_xhat, g_mu, g_lv, g_z, g_pre, g_handle, want_dx=ctx.needs_input_grad[0])
+        return dx, None, None, None
+
+
+def _graph_model(ctx):
+    """The model of an autograd node of this module, if the context still holds the activations of that node's forward."""
+    model = ctx.model_ref()
+    if model is None:
+        raise RuntimeError("the VanillaVAE of this graph no longer exists")
+    if model._fwd_count != ctx.generation:
+        raise RuntimeError("backward through a forward that is no longer the model's last one: the context keeps the "
+                           "activations of one forward only (run backward before the next forward, or one model per graph)")
+    return model
+
+
+class _VAEEncode(torch.autograd.Function):
+    """VanillaVAE.encode (models.py:107-145): the encoder and fc heads only (vae_encode / vae_backward_ex)."""
+
+    @staticmethod
+    def forward(ctx, x, anchor, model):
+        ctx.set_materialize_grads(False)
+        ctx.model_ref = weakref.ref(model)
+        out = model._run_encode(x, train=model.training)
+        ctx.generation = model._fwd_count
+        return out
+
+    @staticmethod
+    def backward(ctx, g_mu, g_lv, g_pre):
+        model = _graph_model(ctx)
+        dx, _ = model._run_backward_ex(None, g_mu, g_lv, None, g_pre, None, want_dx=ctx.needs_input_grad[0])
+        return dx, None, None
+
+
+class _VAEDecode(torch.autograd.Function):
+    """VanillaVAE.decode (models.py:147-175): decoder_input, decoder and final_layer only (vae_decode / vae_backward_ex)."""
+
+    @staticmethod
+    def forward(ctx, z, anchor, model):
+        ctx.set_materialize_grads(False)
+        ctx.model_ref = weakref.ref(model)
+        out = model._run_decode(z, train=model.training)
+        ctx.generation = model._fwd_count
+        return out
+
+    @staticmethod
+    def backward(ctx, g_xhat):
+        model = _graph_model(ctx)
+        _, dz = model._run_backward_ex(g_xhat, None, None, None, None, None, want_dz=ctx.needs_input_grad[0])
+        return dz, None, None
 
 
 class _FusedELBO(torch.autograd.Function):
@@ -450,12 +497,56 @@ class VanillaVAE(nn.Module):
                 _lib.check(_lib.lib().vae_pre_latents(ctx.handle, pre.data_ptr(), self._stream()), "vae_pre_latents")
             else:
                 pre = torch.empty(B, 0, device=dev)
-        self._last = dict(x=x, xhat=xhat, mu=mu, lv=lv, z=z, train=train)
+        self._last = dict(x=x, xhat=xhat, mu=mu, lv=lv, z=z, train=train, B=B)
         return xhat, mu, lv, z, pre
+
+    def _run_encode(self, x: Tensor, train: bool):
+        """vae_encode: the encoder half of _run_forward (same launches: mu / log_var bit-identical).  Returns mu, log_var, pre."""
+        self._check_input(x)
+        x = x.detach().contiguous().float()
+        B, L, dev = x.shape[0], self.latent_dim, x.device
+        ctx = self._context(B)
+        mu, lv, z = (torch.empty(B, L, device=dev) for _ in range(3))
+        self._fwd_count += 1
+        seed = (int(self.eps_seed) + self._fwd_count + _rank() * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+        with self._device_guard():
+            _lib.check(_lib.lib().vae_encode(
+                ctx.handle, x.data_ptr(), B, self._flat.data_ptr(), self._bnflat.data_ptr(), self._nbt.data_ptr(), 0, seed,
+                int(train), mu.data_ptr(), lv.data_ptr(), z.data_ptr(), self._stream()), "vae_encode")
+            if self.materialize_pre_latents:
+                pre = torch.empty(B, self.flattened_size, device=dev)
+                _lib.check(_lib.lib().vae_pre_latents(ctx.handle, pre.data_ptr(), self._stream()), "vae_pre_latents")
+            else:
+                pre = torch.empty(B, 0, device=dev)
+        self._last = dict(kind="encode", x=x, mu=mu, lv=lv, z=z, train=train, B=B)
+        return mu, lv, pre
+
+    def _run_decode(self, z: Tensor, train: bool):
+        """vae_decode: z [B, latent_dim] -> xhat [B,1,H,W]."""
+        self._require_device()
+        z = z.detach().to(self._flat.device, torch.float32).contiguous()
+        if z.dim() != 2 or z.shape[1] != self.latent_dim:
+            raise RuntimeError(f"expected z [B,{self.latent_dim}], got {tuple(z.shape)}")
+        B = z.shape[0]
+        ctx = self._context(B)
+        xhat = torch.empty(B, 1, self.img_size, self.img_size, device=z.device, dtype=torch.float32)
+        self._fwd_count += 1
+        with self._device_guard():
+            _lib.check(_lib.lib().vae_decode(ctx.handle, z.data_ptr(), B, self._flat.data_ptr(), self._bnflat.data_ptr(),
+                                            self._nbt.data_ptr(), int(train), xhat.data_ptr(), self._stream()), "vae_decode")
+        self._last = dict(kind="decode", z=z, xhat=xhat, train=train, B=B)   # (z and xhat stay alive for the backward)
+        return xhat
+
+    def _needs_graph(self, inp: Tensor) -> bool:
+        """Record an autograd node for a call on `inp`: grad mode on and something to differentiate (the reference's modules
+        build a graph whenever a parameter requires grad)."""
+        if not torch.is_grad_enabled():
+            return False
+        return inp.requires_grad or any(p.requires_grad for p in self._named_param_list())
 
     def _run_backward(self, g_xhat, g_mu, g_lv, g_z, g_pre, g_handle, into_gflat: bool = False):
         last = self._last
-        if last is None or not last["train"]:
+        if last is None or not last["train"] or last.get("kind", "forward") != "forward":
             raise RuntimeError("backward needs a train-mode forward of this model")
         c = lambda t: None if t is None else t.contiguous().float()  # noqa: E731
         g_xhat, g_mu, g_lv, g_z, g_pre, g_handle = map(c, (g_xhat, g_mu, g_lv, g_z, g_pre, g_handle))
@@ -468,12 +559,63 @@ class VanillaVAE(nn.Module):
         if not into_gflat:
             self._commit_grads()
 
-    def _commit_grads(self):
-        """param.grad semantics of autograd: assign where grad is None, accumulate otherwise."""
+    # parameters a decode-only / encode-only backward writes (indices into _lib.PARAM_NAMES)
+    _DECODER_PARAMS = frozenset(i for i, n in enumerate(_lib.PARAM_NAMES) if n.split(".")[0] in ("decoder_input", "decoder", "final_layer"))
+    _ENCODER_PARAMS = frozenset(range(len(_lib.PARAM_NAMES))) - _DECODER_PARAMS
+
+    def _run_backward_ex(self, g_xhat, g_mu, g_lv, g_z, g_pre, g_handle, want_dx: bool = False, want_dz: bool = False):
+        """vae_backward_ex: the backward of whichever forward ran last (forward / encode / decode, train or eval mode).
+        Commits the parameter gradients that forward has and returns (dx or None, dz or None).
+
+        f16 storage: the library scales the backward's gradients by a power of two chosen for the mean-reduced ELBO
+        (vae_ctx.h: set_grad_scale).  An arbitrary upstream gradient (a sum-reduced loss, a masked loss on decode(z)) can be
+        far larger, and its scaled products would overflow f16.  So the upstream gradients are first multiplied by a second
+        power of two s, formed on the device (no host sync) from their largest magnitude relative to that of the standard ELBO
+        (1/(B*H*W) on the reconstruction, 1/B on the latent), and every result is multiplied by 1/s afterwards.  Powers of two
+        are exact: the f32 arithmetic is unchanged wherever nothing overflows or underflows."""
+        last = self._last
+        if last is None:
+            raise RuntimeError("backward needs a forward of this model")
+        kind = last.get("kind", "forward")
+        c = lambda t: None if t is None else t.contiguous().float()  # noqa: E731
+        g_xhat, g_mu, g_lv, g_z, g_pre, g_handle = map(c, (g_xhat, g_mu, g_lv, g_z, g_pre, g_handle))
+        B = last["B"]
+        inv_s = None
+        if self.compute_dtype in ("f16", "fp16", "float16", "half"):
+            npix = float(B * self.img_size * self.img_size)
+            mags = [g.abs().amax() * f for g, f in ((g_xhat, npix), (g_mu, B), (g_lv, B), (g_z, B), (g_pre, B), (g_handle, 1.0))
+                    if g is not None and g.numel()]
+            if mags:
+                m = torch.stack(mags).amax()
+                e = torch.where(torch.isfinite(m) & (m > 0), torch.ceil(torch.log2(m)), torch.zeros_like(m)).clamp(-100, 100)
+                s, inv_s = torch.exp2(-e), torch.exp2(e)
+                g_xhat, g_mu, g_lv, g_z, g_pre, g_handle = (None if g is None else g * s
+                                                            for g in (g_xhat, g_mu, g_lv, g_z, g_pre, g_handle))
+        dev = self._flat.device
+        dx = torch.empty(B, 1, self.img_size, self.img_size, device=dev) if want_dx and kind != "decode" else None
+        dz = torch.empty(B, self.latent_dim, device=dev) if want_dz and kind == "decode" else None
+        with self._device_guard():
+            _lib.check(_lib.lib().vae_backward_ex(
+                self._ctx.handle, _lib.ptr(last.get("x")), self._flat.data_ptr(), self._gnew.data_ptr(), _lib.ptr(g_xhat),
+                _lib.ptr(g_handle), _lib.ptr(g_mu), _lib.ptr(g_lv), _lib.ptr(g_z), _lib.ptr(g_pre),
+                float(self._bwd_kld_weight), int(g_handle is not None), _lib.ptr(dx), _lib.ptr(dz), self._stream()), "vae_backward_ex")
+        which = self._DECODER_PARAMS if kind == "decode" else self._ENCODER_PARAMS if kind == "encode" else None
+        if inv_s is not None:
+            for i in (range(len(self._offs)) if which is None else which):
+                self._gnew[self._offs[i]:self._offs[i] + self._sizes[i]].mul_(inv_s)
+            for t in (dx, dz):
+                if t is not None:
+                    t.mul_(inv_s)
+        self._commit_grads(which)
+        return dx, dz
+
+    def _commit_grads(self, which=None):
+        """param.grad semantics of autograd: assign where grad is None, accumulate otherwise.  ``which``: indices of the
+        parameters the backward produced (None: all)."""
         params = self._named_param_list()
         runs, cur = [], None
         for i, p in enumerate(params):
-            if not p.requires_grad:
+            if not p.requires_grad or (which is not None and i not in which):
                 kind = "skip"
             elif p.grad is None:
                 kind = "assign"
@@ -496,7 +638,7 @@ class VanillaVAE(nn.Module):
             elif kind == "add":
                 self._gflat[a:b].add_(self._gnew[a:b])
         for i, p in enumerate(params):
-            if p.requires_grad and p.grad is None:
+            if p.requires_grad and p.grad is None and (which is None or i in which):
                 p.grad = self._gflat[self._offs[i]:self._offs[i] + self._sizes[i]].view(p.shape)
 
     def bind_flat_grads(self):
@@ -509,25 +651,24 @@ class VanillaVAE(nn.Module):
 
     # -- reference API ------------------------------------------------------
     def encode(self, x: Tensor) -> EncoderOutput:
-        """models.py:107-145 (runs the whole fused forward; the decoder half is discarded)."""
-        out = self.forward(x)
-        return out["encoded"]
+        """models.py:107-145: the encoder and the fc heads only (vae_encode; no decoder launch).  mu / log_var are
+        bit-identical to forward()'s.  Differentiable w.r.t. the encoder / fc parameters and x, in train and eval mode."""
+        self._require_device()
+        if self._needs_graph(x):
+            mu, lv, pre = _VAEEncode.apply(x, self._anchor_tensor(x.device), self)
+        else:
+            mu, lv, pre = self._run_encode(x, train=self.training)
+        return EncoderOutput(mu=mu, log_var=lv, pre_latents=pre)
 
     def decode(self, z: Tensor) -> Tensor:
-        """models.py:147-175: latent [B, latent_dim] -> reconstruction [B,1,H,W].  Inference helper (SURVEY.md 8f,
-        N4): runs the decoder kernels only; not differentiable (training differentiates through forward())."""
+        """models.py:147-175: latent [B, latent_dim] -> reconstruction [B,1,H,W] (vae_decode: the decoder kernels only).
+        Differentiable w.r.t. z and the decoder_input / decoder / final_layer parameters, in train mode (batch statistics,
+        running statistics updated once) and eval mode (running statistics), when z requires grad; a z that does not
+        decodes for inference, as sample() does (no graph, whatever the parameters' requires_grad)."""
         self._require_device()
-        z = z.detach().to(self._flat.device, torch.float32).contiguous()
-        if z.dim() != 2 or z.shape[1] != self.latent_dim:
-            raise RuntimeError(f"expected z [B,{self.latent_dim}], got {tuple(z.shape)}")
-        B = z.shape[0]
-        ctx = self._context(B)
-        xhat = torch.empty(B, 1, self.img_size, self.img_size, device=z.device, dtype=torch.float32)
-        with self._device_guard():
-            _lib.check(_lib.lib().vae_decode(ctx.handle, z.data_ptr(), B, self._flat.data_ptr(), self._bnflat.data_ptr(),
-                                            self._nbt.data_ptr(), int(self.training), xhat.data_ptr(), self._stream()), "vae_decode")
-        self._last = None
-        return xhat
+        if torch.is_grad_enabled() and z.requires_grad:
+            return _VAEDecode.apply(z, self._anchor_tensor(self._flat.device), self)
+        return self._run_decode(z, train=self.training)
 
     def log_likelihood(self, x: Tensor, num_samples: int = 64, *, eps: Tensor | None = None, chunk: int | None = None,
                        seed: int | None = None) -> LikelihoodOutput:
@@ -589,7 +730,7 @@ class VanillaVAE(nn.Module):
         if eps is None:
             # torch.randn_like(std) of models.py:182: drawn from torch's device generator
             eps = torch.randn(x.shape[0], self.latent_dim, device=x.device, dtype=torch.float32)
-        if torch.is_grad_enabled() and self.training:
+        if torch.is_grad_enabled() and (self.training or self._needs_graph(x)):
             anchor = self._anchor_tensor(x.device)
             xhat, mu, lv, z, pre, handle = _VAEForward.apply(x, anchor, self, eps)
         else:
@@ -628,7 +769,8 @@ class VanillaVAE(nn.Module):
         """models.py:250-263: z ~ N(0, I) on the host generator, moved to the device, decoded."""
         z = torch.randn(num_samples, self.latent_dim)
         z = z.to(current_device)
-        return self.decode(z)
+        with torch.no_grad():
+            return self.decode(z)
 
     def generate(self, x: Tensor, **kwargs) -> Tensor:
         """models.py:265-272."""
@@ -702,7 +844,7 @@ class VanillaVAE(nn.Module):
                 n, offs, sizes, lrs, b1s, beta2, adam_eps, wd, float(optimizer.grad_scale), optimizer._step + 1, int(exchange),
                 xhat.data_ptr(), mu.data_ptr(), lv.data_ptr(), z.data_ptr(), out3.data_ptr(), self._stream()), "vae_train_step_fused")
         optimizer._stepped()
-        self._last = dict(x=x, xhat=xhat, mu=mu, lv=lv, z=z, train=True)
+        self._last = dict(x=x, xhat=xhat, mu=mu, lv=lv, z=z, train=True, B=B)
         params, views = self._param_grad_views()
         if params[0].grad is not views[0] or params[-1].grad is not views[-1]:   # (bound once: the fused path never unbinds them)
             self.bind_flat_grads()
