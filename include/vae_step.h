@@ -143,6 +143,18 @@ int vae_log_likelihood(vae_ctx* ctx, const float* x, int batch, const float* par
                        int num_samples, int chunk, const float* eps, uint64_t seed,
                        double* log_w, double* log_likelihood, double* elbo, vae_stream_t stream);
 
+/* Latent diagnostics of n posteriors q(z|x_i) = N(mu_i, diag e^{log_var_i}) ([n, latent_dim] f32, 1 <= latent_dim <= 4096): the
+ * aggregate posterior q(z) = 1/n sum_j q(z|x_j), all n components (the query's own included), at draws z[s,i] = eps * exp(0.5 lv_i) + mu_i.
+ * eps [draws,n,L] f32, or NULL: element (s*n+i)*L+d of the device counter generator (seed, stream 7).  Outputs f64, nats:
+ *   log_qz [draws*n]        log q(z_q)
+ *   log_qz_dims [draws*n*L] log q(z_qd)                       (marginal of dimension d)
+ *   per_dim [3*L]           kl_per_dim (mean_i KL_d), var_mu (population variance over i of mu_id), dwkl_per_dim
+ *   scalars [4]             kl, mi = I(x;z), tc (total correlation), dwkl (dimension-wise KL); kl = mi + tc + dwkl
+ * Context-free, on `stream`; every reduction runs in a fixed order (repeated calls are bit-identical).  Its work space, about
+ * (12 + 12 draws) n L bytes (more when small shapes split the component range), comes from the stream-ordered allocator. */
+int vae_latent_stats(const float* mu, const float* log_var, int64_t n, int latent_dim, int draws, const float* eps, uint64_t seed,
+                     double* log_qz, double* log_qz_dims, double* per_dim, double* scalars, vae_stream_t stream);
+
 /* loss.backward() (train.py:650) for the last train-mode forward.
  *   grads: flat f32 buffer, same layout as params; every tensor is overwritten.
  *   use_std: 1 adds the gradient of the standard ELBO of vae_loss (reconstruction term fused in

@@ -72,6 +72,7 @@ def lib():
     _sig(L.vae_elbo_generic_ex, i32, [p, p, p, p, i64, i32, i32, f32, i32, p, p, p, p, p])
     _sig(L.vae_set_recon_loss, i32, [p, i32])
     _sig(L.vae_log_likelihood, i32, [p, p, i32, p, p, i32, i32, p, u64, p, p, p, p])
+    _sig(L.vae_latent_stats, i32, [p, p, i64, i32, i32, p, u64, p, p, p, p, p])
     _sig(L.vae_backward, i32, [p, p, p, p, p, p, p, p, p, p, f32, i32, p])
     _sig(L.vae_backward_part, i32, [p, p, p, p, p, p, p, p, p, p, f32, i32, i32, p])
     _sig(L.vae_encode, i32, [p, p, i32, p, p, p, p, u64, i32, p, p, p, p])
@@ -105,7 +106,7 @@ def lib():
 EXPORTS = [
     "vae_last_error", "vae_abi_version", "vae_param_layout", "vae_bn_layout", "vae_create", "vae_destroy",
     "vae_workspace_bytes", "vae_forward", "vae_decode", "vae_pre_latents", "vae_last_eps", "vae_loss", "vae_loss_deferred", "vae_elbo_generic",
-    "vae_set_recon_loss", "vae_elbo_generic_ex", "vae_log_likelihood",
+    "vae_set_recon_loss", "vae_elbo_generic_ex", "vae_log_likelihood", "vae_latent_stats",
     "vae_backward", "vae_backward_part", "vae_encode", "vae_backward_ex", "vae_comm_stream", "vae_comm_unique_id", "vae_comm_init", "vae_comm_world",
     "vae_comm_destroy", "vae_allreduce_grads", "vae_broadcast_state", "vae_adamw_step", "vae_train_step", "vae_train_step_fused", "vae_synth_pianoroll", "vae_expand_stimuli", "vae_profile",
     "vae_profile_report", "vae_profile_sequence", "vae_profile_timeline", "vae_debug_stamps", "vae_debug_tensor",

@@ -5,6 +5,7 @@
 #include "vae_ctx.h"
 #include "edge_kernels.cuh"
 #include "loglik.cuh"
+#include "latent_stats.cuh"
 
 static thread_local std::string g_err;
 int vae_set_error(const char* what, const char* why) {
@@ -529,6 +530,74 @@ extern "C" int vae_elbo_generic_ex(const float* xhat, const float* target, const
 extern "C" int vae_elbo_generic(const float* xhat, const float* target, const float* mu, const float* lv, int64_t n, int B, int L,
                                 float kld_weight, float* out3, float* g_xhat, float* g_mu, float* g_lv, vae_stream_t stream) {
     return vae_elbo_generic_ex(xhat, target, mu, lv, n, B, L, kld_weight, VAE_RECON_BCE, out3, g_xhat, g_mu, g_lv, stream);
+}
+
+// Latent diagnostics (latent_stats.cuh).  Launches: prep (tables, z), joint and dims pairwise kernels over split component ranges,
+// two merges, the per-dimension moments, the scalar combine.  Work space from the stream-ordered allocator, freed on the stream.
+// The split counts depend on (n, L, draws) only, so a given shape always reduces in the same order.
+extern "C" int vae_latent_stats(const float* mu, const float* lv, int64_t n, int L, int S, const float* eps, uint64_t seed,
+                                double* log_qz, double* log_qz_dims, double* per_dim, double* scalars, vae_stream_t stream) {
+    if (!mu || !lv || !log_qz || !log_qz_dims || !per_dim || !scalars) return vae_set_error("vae_latent_stats", "null tensor pointer");
+    if (n < 1 || n > (int64_t)1 << 30) return vae_set_error("vae_latent_stats", "n must be in [1, 2^30]");
+    if (L < 1 || L > 4096) return vae_set_error("vae_latent_stats", "latent_dim must be in [1, 4096]");
+    if (S < 1) return vae_set_error("vae_latent_stats", "draws must be >= 1");
+    const long N = (long)n, SN = (long)S * N;
+    if (SN > ((long)1 << 40) / L) return vae_set_error("vae_latent_stats", "draws * n * latent_dim too large");
+    hipStream_t st = (hipStream_t)stream;
+    // split of the component range: enough waves for the 256 CUs, at least 256 components per split, at most 64 splits
+    auto splits = [&](long waves, long target, int tile, int& jper) {
+        long ns = std::max<long>(1, std::min<long>({(target + waves - 1) / waves, (N + 255) / 256, 64}));
+        jper = (int)(((N + ns - 1) / ns + tile - 1) / tile * tile);
+        return (int)((N + jper - 1) / jper);
+    };
+    const long jblocks = (SN + 256 * LS_QR - 1) / (256 * LS_QR);
+    int jper_j = 0;
+    const int nsj = splits(jblocks * 4, 2048, LS_JT, jper_j);
+    const int DB = std::min(L, LS_DB), QG = 256 / DB, ndt = (L + DB - 1) / DB;
+    const long dblocks = (long)ndt * ((SN + (long)QG * LS_QR - 1) / ((long)QG * LS_QR));
+    int jper_d = 0;
+    const int nsd = splits(dblocks * 4, 4096, LS_JD, jper_d);
+    if (jblocks > INT32_MAX || dblocks > INT32_MAX) return vae_set_error("vae_latent_stats", "grid too large");
+    const size_t nl = (size_t)N * L, snl = (size_t)SN * L;
+    size_t off[8], tot = 0;
+    const size_t sz[7] = {snl * 4, nl * 8, nl * 4, (size_t)N * 4, (size_t)nsj * SN * 8, (size_t)nsd * snl * 8, (size_t)4 * L * 8};
+    for (int k = 0; k < 7; ++k) { off[k] = tot; tot += (sz[k] + 255) / 256 * 256; }
+    void* ws = nullptr;
+    HIP_CHECK_RET(hipMallocAsync(&ws, tot, st));
+    char* base = static_cast<char*>(ws);
+    float* z = reinterpret_cast<float*>(base + off[0]);
+    float2* mh = reinterpret_cast<float2*>(base + off[1]);
+    float* c2 = reinterpret_cast<float*>(base + off[2]);
+    float* cj = reinterpret_cast<float*>(base + off[3]);
+    float2* pj = reinterpret_cast<float2*>(base + off[4]);
+    float2* pd = reinterpret_cast<float2*>(base + off[5]);
+    double* dstat = reinterpret_cast<double*>(base + off[6]);
+    const double lnN = log((double)N);
+    auto run = [&]() -> int {
+        hipLaunchKernelGGL(lstat_prep_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, mu, lv, eps, (unsigned long long)seed,
+                           (int)N, L, S, z, mh, c2, cj);
+        LAUNCH_CHECK("lstat_prep_kernel");
+        hipLaunchKernelGGL(lstat_joint_kernel, dim3((unsigned)jblocks, nsj), dim3(256), 0, st, z, mh, cj, SN, (int)N, L, jper_j, pj);
+        LAUNCH_CHECK("lstat_joint_kernel");
+        hipLaunchKernelGGL(lstat_dims_kernel, dim3((unsigned)dblocks, nsd), dim3(256), 0, st, z, mh, c2, SN, (int)N, L, DB, ndt, jper_d, pd);
+        LAUNCH_CHECK("lstat_dims_kernel");
+        hipLaunchKernelGGL(lstat_merge_kernel, dim3((unsigned)std::min<long>((SN + 255) / 256, 4096)), dim3(256), 0, st, pj, nsj, SN, lnN,
+                           log_qz);
+        LAUNCH_CHECK("lstat_merge_kernel");
+        hipLaunchKernelGGL(lstat_merge_kernel, dim3((unsigned)std::min<long>((long)(snl + 255) / 256, 8192)), dim3(256), 0, st, pd, nsd,
+                           (long)snl, lnN, log_qz_dims);
+        LAUNCH_CHECK("lstat_merge_kernel");
+        hipLaunchKernelGGL(lstat_moments_kernel, dim3(L), dim3(256), 0, st, mu, lv, log_qz_dims, (int)N, SN, L, per_dim, dstat);
+        LAUNCH_CHECK("lstat_moments_kernel");
+        hipLaunchKernelGGL(lstat_final_kernel, dim3(1), dim3(256), 0, st, log_qz, SN, dstat, L, scalars);
+        LAUNCH_CHECK("lstat_final_kernel");
+        return 0;
+    };
+    const int rc = run();
+    const hipError_t fe = hipFreeAsync(ws, st);
+    if (rc) return rc;
+    if (fe != hipSuccess) return vae_set_error("hipFreeAsync", hipGetErrorString(fe));
+    return 0;
 }
 
 // A non-blocking stream owned by the context, ordered after everything enqueued on `stream` so far.  Work the caller

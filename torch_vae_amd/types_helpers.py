@@ -27,3 +27,16 @@ class LikelihoodOutput(TypedDict):
     log_likelihood: Tensor    # [B] float64: importance-weighted estimate of log p(x) (nats)
     elbo: Tensor              # [B] float64: per-sample evidence lower bound (nats)
     log_weights: Tensor       # [K, B] float64: log p(x|z_k) + log p(z_k) - log q(z_k|x)
+
+
+class LatentStatsOutput(TypedDict):
+    kl: Tensor                # 0-d float64: mean KL(q(z|x) || N(0, I)) (nats)
+    mi: Tensor                # 0-d float64: mutual information I(x;z) under the aggregate posterior (nats)
+    tc: Tensor                # 0-d float64: total correlation of the aggregate posterior (nats)
+    dwkl: Tensor              # 0-d float64: dimension-wise KL, sum_d KL(q(z_d) || N(0, 1)) (nats); kl = mi + tc + dwkl
+    active_units: int         # #{d : var_mu[d] > active_threshold}
+    kl_per_dim: Tensor        # [L] float64
+    var_mu: Tensor            # [L] float64: population variance over the rolls of mu_d
+    dwkl_per_dim: Tensor      # [L] float64
+    log_qz: Tensor            # [S, N] float64: log q(z) at each draw
+    log_qz_dims: Tensor       # [S, N, L] float64: log q(z_d) at each draw
