@@ -222,6 +222,28 @@ int vae_adamw_step(float* params, const float* grads, float* exp_avg, float* exp
                    double beta2, double eps, double weight_decay, float grad_scale, int step,
                    vae_stream_t stream);
 
+/* Gradient-norm clipping and non-finite step skipping (torch.nn.utils.clip_grad_norm_ in front of AdamW, the skip of
+ * torch's GradScaler), with no host synchronisation: the norm, the clip decision and the AdamW step count live on the device.
+ *   norm = || g * grad_scale ||_2 over the ranges, all groups together, summed in f64 in a fixed order (deterministic:
+ *          the grid does not depend on the device; every rank of a data-parallel job takes the same decision);
+ *   coef = min(1, max_grad_norm / (norm + 1e-6)) in f64, rounded once to f32; max_grad_norm <= 0: no clipping (coef 1);
+ *   skip_nonfinite and a non-finite norm: parameters and moments untouched, *step held, *skipped += 1; otherwise
+ *   *step += 1 and AdamW runs with g * grad_scale * coef and the bias corrections of the new *step.
+ * The gradient buffer keeps the unclipped gradient.  `scratch`: VAE_GRAD_CLIP_SCRATCH_BYTES of device memory, 16-byte
+ * aligned, owned by the caller and not used by anything else until the stream has passed the call.  step (the device count
+ * of updates so far), norm_out and skipped are device scalars.  Bad arguments (ngroups not 1 or 2, a null pointer, a NaN
+ * max_grad_norm) return -1 before anything is enqueued. */
+#define VAE_GRAD_CLIP_SCRATCH_BYTES 8192
+/* The norm alone (a diagnostic): *norm_out = || g * grad_scale ||_2 over the ranges. */
+int vae_grad_norm(const float* grads, int ngroups, const int64_t* offsets, const int64_t* sizes, float grad_scale,
+                  double* norm_out, void* scratch, vae_stream_t stream);
+/* vae_adamw_step with the clipping / skipping above; the host's 1-based step is replaced by the device counter `step`. */
+int vae_adamw_step_clipped(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int ngroups,
+                           const int64_t* offsets, const int64_t* sizes, const double* lrs, const double* beta1s,
+                           double beta2, double eps, double weight_decay, float grad_scale, double max_grad_norm,
+                           int skip_nonfinite, int64_t* step, double* norm_out, int64_t* skipped, void* scratch,
+                           vae_stream_t stream);
+
 /* One whole training step (train.py:634-659 minus logging): forward, loss, backward, AdamW. */
 int vae_train_step(vae_ctx* ctx, const float* x, int batch, float* params, float* grads, float* exp_avg,
                    float* exp_avg_sq, float* bn_running, int64_t* num_batches_tracked, const float* eps,
@@ -242,6 +264,17 @@ int vae_train_step_fused(vae_ctx* ctx, const float* x, int batch, float* params,
                          const int64_t* sizes, const double* lrs, const double* beta1s, double beta2, double adam_eps,
                          double weight_decay, float grad_scale, int step, int exchange, float* xhat, float* mu,
                          float* log_var, float* z, float* out3, vae_stream_t stream);
+/* vae_train_step_fused with the clipping / skipping of vae_adamw_step_clipped (the host step replaced by the device
+ * counter): the norm is taken AFTER the gradient exchange.  With exchange 2 it waits for every bucket and both groups'
+ * AdamW follow it, so the update of one group no longer overlaps the other bucket's all-reduce. */
+int vae_train_step_fused_clipped(vae_ctx* ctx, const float* x, int batch, float* params, float* grads, float* exp_avg,
+                                 float* exp_avg_sq, float* bn_running, int64_t* num_batches_tracked, const float* eps,
+                                 uint64_t seed, float kld_weight, int ngroups, const int64_t* offsets,
+                                 const int64_t* sizes, const double* lrs, const double* beta1s, double beta2,
+                                 double adam_eps, double weight_decay, float grad_scale, double max_grad_norm,
+                                 int skip_nonfinite, int64_t* step, double* norm_out, int64_t* skipped, void* scratch,
+                                 int exchange, float* xhat, float* mu, float* log_var, float* z, float* out3,
+                                 vae_stream_t stream);
 
 /* Synthetic pianoroll/line batch with the distribution of data_generators.py:45-77
  * (called as at :97-104), seeded; x [B,1,H,H] f32 in {0,1}.  Device-side generator. */

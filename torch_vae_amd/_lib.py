@@ -20,6 +20,7 @@ DTYPE_F16 = 2
 RECON_BCE = 0
 RECON_MSE = 1
 COMM_ID_BYTES = 128
+GRAD_CLIP_SCRATCH_BYTES = 8192   # include/vae_step.h: VAE_GRAD_CLIP_SCRATCH_BYTES
 
 PARAM_NAMES = (
     [f"encoder.{i}.{j}" for i in range(4) for j in ("0.weight", "0.bias", "1.weight", "1.bias")]
@@ -85,10 +86,14 @@ def lib():
     _sig(L.vae_allreduce_grads, i32, [p, p, i32, i64p, i64p, i32, p])
     _sig(L.vae_broadcast_state, i32, [p, p, p, p, i32, p])
     _sig(L.vae_adamw_step, i32, [p, p, p, p, i32, i64p, i64p, f64p, f64p, f64, f64, f64, f32, i32, p])
+    _sig(L.vae_grad_norm, i32, [p, i32, i64p, i64p, f32, p, p, p])
+    _sig(L.vae_adamw_step_clipped, i32, [p, p, p, p, i32, i64p, i64p, f64p, f64p, f64, f64, f64, f32, f64, i32, p, p, p, p, p])
     _sig(L.vae_train_step, i32, [p, p, i32, p, p, p, p, p, p, p, u64, f32, i32, i64p, i64p, f64p, f64p, f64, f64, f64,
                                  i32, p, p, p, p, p, p])
     _sig(L.vae_train_step_fused, i32, [p, p, i32, p, p, p, p, p, p, p, u64, f32, i32, i64p, i64p, f64p, f64p, f64, f64, f64, f32,
                                        i32, i32, p, p, p, p, p, p])
+    _sig(L.vae_train_step_fused_clipped, i32, [p, p, i32, p, p, p, p, p, p, p, u64, f32, i32, i64p, i64p, f64p, f64p, f64, f64, f64,
+                                               f32, f64, i32, p, p, p, p, i32, p, p, p, p, p, p])
     _sig(L.vae_synth_pianoroll, i32, [p, i32, i32, u64, p])
     _sig(L.vae_expand_stimuli, i32, [p, i32, p, i64, p])
     _sig(L.vae_profile, i32, [p, i32])
@@ -108,7 +113,8 @@ EXPORTS = [
     "vae_workspace_bytes", "vae_forward", "vae_decode", "vae_pre_latents", "vae_last_eps", "vae_loss", "vae_loss_deferred", "vae_elbo_generic",
     "vae_set_recon_loss", "vae_elbo_generic_ex", "vae_log_likelihood", "vae_latent_stats",
     "vae_backward", "vae_backward_part", "vae_encode", "vae_backward_ex", "vae_comm_stream", "vae_comm_unique_id", "vae_comm_init", "vae_comm_world",
-    "vae_comm_destroy", "vae_allreduce_grads", "vae_broadcast_state", "vae_adamw_step", "vae_train_step", "vae_train_step_fused", "vae_synth_pianoroll", "vae_expand_stimuli", "vae_profile",
+    "vae_comm_destroy", "vae_allreduce_grads", "vae_broadcast_state", "vae_adamw_step", "vae_train_step", "vae_train_step_fused",
+    "vae_grad_norm", "vae_adamw_step_clipped", "vae_train_step_fused_clipped", "vae_synth_pianoroll", "vae_expand_stimuli", "vae_profile",
     "vae_profile_report", "vae_profile_sequence", "vae_profile_timeline", "vae_debug_stamps", "vae_debug_tensor",
     "vae_selftest_tr16", "vae_set_option",
 ]

@@ -867,8 +867,13 @@ struct AdamArgs {
     float beta2, omb2, eps, grad_scale; int step;
 };
 // One element of torch.optim.AdamW's single-tensor update (decoupled decay, bias corrections as torch computes them).
-__device__ __forceinline__ void adamw_one(float& p, float g, float& m, float& v, const AdamGroup& gr, const AdamArgs& a, float decay) {
+// CLIP (grad_clip.cuh): the scaled gradient is multiplied by the clip coefficient of torch.nn.utils.clip_grad_norm_ first;
+// coef == 1.f leaves every bit of the update as without it.
+template <bool CLIP = false>
+__device__ __forceinline__ void adamw_one(float& p, float g, float& m, float& v, const AdamGroup& gr, const AdamArgs& a, float decay,
+                                          float coef = 1.f) {
     g *= a.grad_scale;
+    if (CLIP) g *= coef;
     p *= decay;
     m = m * gr.beta1 + gr.omb1 * g;
     v = v * a.beta2 + a.omb2 * g * g;
@@ -878,8 +883,8 @@ __device__ __forceinline__ void adamw_one(float& p, float g, float& m, float& v,
 // 16-byte accesses (the flat buffers' ranges start on 256-byte boundaries); a range whose length is not a multiple of four
 // finishes with scalar elements.  The bias corrections arrive as kernel arguments: computed per thread (two f64 pow, a sqrt and a
 // division each) they cost more than the update itself.
-static __global__ void adamw_kernel(AdamArgs a) {
-    const AdamGroup gr = a.grp[blockIdx.y];
+template <bool CLIP = false>
+__device__ __forceinline__ void adamw_range(const AdamArgs& a, const AdamGroup& gr, float coef = 1.f) {
     const float decay = gr.decay;
     const long n4 = (gr.off & 3) == 0 ? gr.n >> 2 : 0;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
@@ -887,16 +892,17 @@ static __global__ void adamw_kernel(AdamArgs a) {
         f32x4 p = *reinterpret_cast<const f32x4*>(a.p + k), m = *reinterpret_cast<const f32x4*>(a.m + k), v = *reinterpret_cast<const f32x4*>(a.v + k);
         const f32x4 g = *reinterpret_cast<const f32x4*>(a.g + k);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) { float pe = p[e], me = m[e], ve = v[e]; adamw_one(pe, g[e], me, ve, gr, a, decay); p[e] = pe; m[e] = me; v[e] = ve; }
+        for (int e = 0; e < 4; ++e) { float pe = p[e], me = m[e], ve = v[e]; adamw_one<CLIP>(pe, g[e], me, ve, gr, a, decay, coef); p[e] = pe; m[e] = me; v[e] = ve; }
         *reinterpret_cast<f32x4*>(a.p + k) = p; *reinterpret_cast<f32x4*>(a.m + k) = m; *reinterpret_cast<f32x4*>(a.v + k) = v;
     }
     for (long i = 4 * n4 + (long)blockIdx.x * blockDim.x + threadIdx.x; i < gr.n; i += (long)gridDim.x * blockDim.x) {
         const long k = gr.off + i;
         float pe = a.p[k], me = a.m[k], ve = a.v[k];
-        adamw_one(pe, a.g[k], me, ve, gr, a, decay);
+        adamw_one<CLIP>(pe, a.g[k], me, ve, gr, a, decay, coef);
         a.p[k] = pe; a.m[k] = me; a.v[k] = ve;
     }
 }
+static __global__ void adamw_kernel(AdamArgs a) { adamw_range(a, a.grp[blockIdx.y]); }
 
 // ---------------------------------------------------------------------------
 // counter-based generator restated in oracle/vae_oracle.py (splitmix64 of seed, stream, counter)

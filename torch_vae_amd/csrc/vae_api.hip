@@ -6,6 +6,7 @@
 #include "edge_kernels.cuh"
 #include "loglik.cuh"
 #include "latent_stats.cuh"
+#include "grad_clip.cuh"
 
 static thread_local std::string g_err;
 int vae_set_error(const char* what, const char* why) {
@@ -660,6 +661,83 @@ extern "C" int vae_adamw_step(float* params, const float* grads, float* m, float
     return 0;
 }
 
+// Gradient clipping / non-finite skipping (grad_clip.cuh).  The device-side arguments of the clipped update.
+struct ClipArgs {
+    double max_grad_norm; int skip_nonfinite;
+    int64_t* step; double* norm_out; int64_t* skipped; void* scratch;
+};
+static int check_clip_args(const char* what, int ngroups, const int64_t* offsets, const int64_t* sizes, const ClipArgs& k) {
+    if (ngroups < 1 || ngroups > 2) return vae_set_error(what, "1 or 2 groups");
+    if (!offsets || !sizes) return vae_set_error(what, "null offsets / sizes");
+    for (int i = 0; i < ngroups; ++i)
+        if (offsets[i] < 0 || sizes[i] < 1) return vae_set_error(what, "empty or negative range");
+    if (k.max_grad_norm != k.max_grad_norm) return vae_set_error(what, "max_grad_norm is NaN");
+    if (!k.step || !k.norm_out || !k.skipped || !k.scratch) return vae_set_error(what, "null device pointer (step, norm_out, skipped, scratch)");
+    if ((uintptr_t)k.scratch % 16) return vae_set_error(what, "scratch must be 16-byte aligned");
+    return 0;
+}
+// sum of squares + finalize on `st`; `clip` null: the norm alone
+static int launch_grad_norm(const float* grads, int ngroups, const int64_t* offsets, const int64_t* sizes, float grad_scale,
+                            const double* lrs, const double* beta1s, double beta2, const ClipArgs& k, bool clip, hipStream_t st) {
+    GradSumsqArgs s;
+    s.g = grads; s.grad_scale = grad_scale; s.partial = static_cast<double*>(k.scratch);
+    for (int i = 0; i < ngroups; ++i) { s.off[i] = offsets[i]; s.n[i] = sizes[i]; }
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(GCLIP_BLOCKS, ngroups), dim3(256), 0, st, s);
+    LAUNCH_CHECK("grad_sumsq_kernel");
+    GradClipArgs f = {};
+    f.partial = s.partial; f.ngrp = ngroups; f.max_norm = k.max_grad_norm; f.skip = k.skip_nonfinite ? 1 : 0;
+    f.step = clip ? reinterpret_cast<long long*>(k.step) : nullptr; f.skipped = reinterpret_cast<long long*>(k.skipped);
+    f.norm_out = k.norm_out; f.beta2 = beta2;
+    for (int i = 0; i < ngroups && clip; ++i) { f.lr[i] = lrs[i]; f.beta1[i] = beta1s[i]; }
+    f.rec = reinterpret_cast<GradClipRecord*>(static_cast<char*>(k.scratch) + GCLIP_RECORD_OFF);
+    hipLaunchKernelGGL(grad_clip_finalize_kernel, dim3(1), dim3(256), 0, st, f);
+    LAUNCH_CHECK("grad_clip_finalize_kernel");
+    return 0;
+}
+static int adamw_step_clipped(float* params, const float* grads, float* m, float* v, int ngroups, const int64_t* offsets,
+                              const int64_t* sizes, const double* lrs, const double* beta1s, double beta2, double eps, double weight_decay,
+                              float grad_scale, const ClipArgs& k, hipStream_t st) {
+    if (launch_grad_norm(grads, ngroups, offsets, sizes, grad_scale, lrs, beta1s, beta2, k, true, st)) return -1;
+    AdamArgs a;
+    // vae_adamw_step's scalars; step_size and inv_sqrt_bc2 come from the record (the step count lives on the device)
+    a.p = params; a.g = grads; a.m = m; a.v = v; a.ngrp = ngroups; a.beta2 = (float)beta2; a.omb2 = (float)(1.0 - beta2); a.eps = (float)eps;
+    a.grad_scale = grad_scale; a.step = 0;
+    long nmax = 0;
+    for (int i = 0; i < ngroups; ++i) {
+        a.grp[i].off = offsets[i]; a.grp[i].n = sizes[i]; nmax = std::max<long>(nmax, sizes[i]);
+        a.grp[i].beta1 = (float)beta1s[i]; a.grp[i].omb1 = (float)(1.0 - beta1s[i]); a.grp[i].decay = (float)(1.0 - lrs[i] * weight_decay);
+        a.grp[i].step_size = 0.f; a.grp[i].inv_sqrt_bc2 = 0.f;
+    }
+    const GradClipRecord* rec = reinterpret_cast<const GradClipRecord*>(static_cast<const char*>(k.scratch) + GCLIP_RECORD_OFF);
+    hipLaunchKernelGGL(adamw_clipped_kernel, dim3((unsigned)std::min<long>((nmax / 4 + 255) / 256 + 1, 2048), ngroups), dim3(256), 0, st, a, rec);
+    LAUNCH_CHECK("adamw_clipped_kernel");
+    return 0;
+}
+
+extern "C" int vae_grad_norm(const float* grads, int ngroups, const int64_t* offsets, const int64_t* sizes, float grad_scale,
+                             double* norm_out, void* scratch, vae_stream_t stream) {
+    if (!grads) return vae_set_error("vae_grad_norm", "null gradient buffer");
+    if (ngroups < 1 || ngroups > 2) return vae_set_error("vae_grad_norm", "1 or 2 groups");
+    if (!offsets || !sizes) return vae_set_error("vae_grad_norm", "null offsets / sizes");
+    for (int i = 0; i < ngroups; ++i)
+        if (offsets[i] < 0 || sizes[i] < 1) return vae_set_error("vae_grad_norm", "empty or negative range");
+    if (!norm_out || !scratch) return vae_set_error("vae_grad_norm", "null device pointer (norm_out, scratch)");
+    if ((uintptr_t)scratch % 16) return vae_set_error("vae_grad_norm", "scratch must be 16-byte aligned");
+    ClipArgs k = {0.0, 0, nullptr, norm_out, nullptr, scratch};
+    return launch_grad_norm(grads, ngroups, offsets, sizes, grad_scale, nullptr, nullptr, 0.0, k, false, (hipStream_t)stream);
+}
+
+extern "C" int vae_adamw_step_clipped(float* params, const float* grads, float* m, float* v, int ngroups, const int64_t* offsets,
+                                      const int64_t* sizes, const double* lrs, const double* beta1s, double beta2, double eps,
+                                      double weight_decay, float grad_scale, double max_grad_norm, int skip_nonfinite, int64_t* step,
+                                      double* norm_out, int64_t* skipped, void* scratch, vae_stream_t stream) {
+    const ClipArgs k = {max_grad_norm, skip_nonfinite, step, norm_out, skipped, scratch};
+    if (check_clip_args("vae_adamw_step_clipped", ngroups, offsets, sizes, k)) return -1;
+    if (!params || !grads || !m || !v || !lrs || !beta1s) return vae_set_error("vae_adamw_step_clipped", "null pointer argument");
+    return adamw_step_clipped(params, grads, m, v, ngroups, offsets, sizes, lrs, beta1s, beta2, eps, weight_decay, grad_scale, k,
+                              (hipStream_t)stream);
+}
+
 extern "C" int vae_train_step(vae_ctx* c, const float* x, int B, float* params, float* grads, float* m, float* v, float* bn_running,
                               int64_t* nbt, const float* eps, uint64_t seed, float kld_weight, int ngroups, const int64_t* offsets,
                               const int64_t* sizes, const double* lrs, const double* beta1s, double beta2, double adam_eps,
@@ -682,11 +760,13 @@ extern "C" int vae_train_step(vae_ctx* c, const float* x, int B, float* params, 
 //      group runs while the other group's all-reduce is still in flight (train.py:165-166,201,663 prepare this data-parallel
 //      layout; the reference itself never exchanges).  Same arithmetic as 1: results are bit-identical.
 // Modes 1 and 2 need vae_comm_init.  Outputs (xhat, mu, log_var, z, out3) are caller-owned as in vae_forward / vae_loss.
-extern "C" int vae_train_step_fused(vae_ctx* c, const float* x, int B, float* params, float* grads, float* m, float* v, float* bn_running,
-                                    int64_t* nbt, const float* eps, uint64_t seed, float kld_weight, int ngroups, const int64_t* offsets,
-                                    const int64_t* sizes, const double* lrs, const double* beta1s, double beta2, double adam_eps,
-                                    double weight_decay, float grad_scale, int step, int exchange, float* xhat, float* mu, float* lv,
-                                    float* z, float* out3, vae_stream_t stream) {
+// `clip` (vae_train_step_fused_clipped): the gradient norm runs after the exchange and the AdamW of every group behind it; with
+// exchange 2 that means behind BOTH buckets' events - the update of one group no longer overlaps the other bucket's all-reduce.
+static int train_step_fused(vae_ctx* c, const float* x, int B, float* params, float* grads, float* m, float* v, float* bn_running,
+                            int64_t* nbt, const float* eps, uint64_t seed, float kld_weight, int ngroups, const int64_t* offsets,
+                            const int64_t* sizes, const double* lrs, const double* beta1s, double beta2, double adam_eps,
+                            double weight_decay, float grad_scale, int step, const ClipArgs* clip, int exchange, float* xhat, float* mu,
+                            float* lv, float* z, float* out3, vae_stream_t stream) {
     if (!c) return vae_set_error("vae_train_step_fused", "null ctx");
     if (exchange < 0 || exchange > 2) return vae_set_error("vae_train_step_fused", "exchange must be 0, 1 or 2");
     if (exchange && !c->nccl_comm) return vae_set_error("vae_train_step_fused", "gradient exchange without a communicator: call vae_comm_init first");
@@ -697,6 +777,7 @@ extern "C" int vae_train_step_fused(vae_ctx* c, const float* x, int B, float* pa
     if (exchange != 2) {
         if (vae_backward(c, x, params, grads, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, kld_weight, 1, stream)) return -1;
         if (exchange == 1 && vae_allreduce_grads(c, grads, ngroups, offsets, sizes, 1, stream)) return -1;
+        if (clip) return adamw_step_clipped(params, grads, m, v, ngroups, offsets, sizes, lrs, beta1s, beta2, adam_eps, weight_decay, grad_scale, *clip, st);
         if (ngroups > 0 && vae_adamw_step(params, grads, m, v, ngroups, offsets, sizes, lrs, beta1s, beta2, adam_eps, weight_decay, grad_scale, step, stream)) return -1;
         return 0;
     }
@@ -714,12 +795,38 @@ extern "C" int vae_train_step_fused(vae_ctx* c, const float* x, int B, float* pa
         if (vae_allreduce_grads(c, grads, last, offsets, sizes, 1, cs)) return -1;
         for (int i = 0; i < last; ++i) HIP_CHECK_RET(hipEventRecord(c->ev_bucket[i], (hipStream_t)cs));
     }
+    if (clip) {                                                                  // the norm needs every bucket
+        for (int i = last; i >= 0; --i) HIP_CHECK_RET(hipStreamWaitEvent(st, c->ev_bucket[i], 0));
+        c->comm_busy = 0;
+        return adamw_step_clipped(params, grads, m, v, ngroups, offsets, sizes, lrs, beta1s, beta2, adam_eps, weight_decay, grad_scale, *clip, st);
+    }
     for (int i = last; i >= 0; --i) {                                            // decoder first: its bucket has long arrived
         HIP_CHECK_RET(hipStreamWaitEvent(st, c->ev_bucket[i], 0));
         if (vae_adamw_step(params, grads, m, v, 1, offsets + i, sizes + i, lrs + i, beta1s + i, beta2, adam_eps, weight_decay, grad_scale, step, stream)) return -1;
     }
     c->comm_busy = 0;                                                            // every piece of work on the communication stream has been waited for
     return 0;
+}
+extern "C" int vae_train_step_fused(vae_ctx* c, const float* x, int B, float* params, float* grads, float* m, float* v, float* bn_running,
+                                    int64_t* nbt, const float* eps, uint64_t seed, float kld_weight, int ngroups, const int64_t* offsets,
+                                    const int64_t* sizes, const double* lrs, const double* beta1s, double beta2, double adam_eps,
+                                    double weight_decay, float grad_scale, int step, int exchange, float* xhat, float* mu, float* lv,
+                                    float* z, float* out3, vae_stream_t stream) {
+    return train_step_fused(c, x, B, params, grads, m, v, bn_running, nbt, eps, seed, kld_weight, ngroups, offsets, sizes, lrs, beta1s, beta2,
+                            adam_eps, weight_decay, grad_scale, step, nullptr, exchange, xhat, mu, lv, z, out3, stream);
+}
+extern "C" int vae_train_step_fused_clipped(vae_ctx* c, const float* x, int B, float* params, float* grads, float* m, float* v,
+                                            float* bn_running, int64_t* nbt, const float* eps, uint64_t seed, float kld_weight, int ngroups,
+                                            const int64_t* offsets, const int64_t* sizes, const double* lrs, const double* beta1s, double beta2,
+                                            double adam_eps, double weight_decay, float grad_scale, double max_grad_norm, int skip_nonfinite,
+                                            int64_t* step, double* norm_out, int64_t* skipped, void* scratch, int exchange, float* xhat,
+                                            float* mu, float* lv, float* z, float* out3, vae_stream_t stream) {
+    const ClipArgs k = {max_grad_norm, skip_nonfinite, step, norm_out, skipped, scratch};
+    if (check_clip_args("vae_train_step_fused_clipped", ngroups, offsets, sizes, k)) return -1;   // (before anything is enqueued)
+    if (!c) return vae_set_error("vae_train_step_fused_clipped", "null ctx");
+    if (!params || !grads || !m || !v || !lrs || !beta1s) return vae_set_error("vae_train_step_fused_clipped", "null pointer argument");
+    return train_step_fused(c, x, B, params, grads, m, v, bn_running, nbt, eps, seed, kld_weight, ngroups, offsets, sizes, lrs, beta1s, beta2,
+                            adam_eps, weight_decay, grad_scale, 1, &k, exchange, xhat, mu, lv, z, out3, stream);
 }
 
 // diagnostic: phase stamps of the pipelined down kernel for one layer ("encoder.3", epi) into out[grid*4*6]

@@ -836,13 +836,22 @@ class VanillaVAE(nn.Module):
         self._fwd_count += 1
         seed = (int(self.eps_seed) + self._fwd_count + _rank() * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
         n, offs, sizes, lrs, b1s, beta2, adam_eps, wd = optimizer._step_args()
+        clip = optimizer._clip_args()   # (max_grad_norm / skip_nonfinite: norm, decision and step count on the device)
         self._bwd_kld_weight = float(self.kld_weight)
         with self._device_guard():
-            _lib.check(_lib.lib().vae_train_step_fused(
-                ctx.handle, x.data_ptr(), B, self._flat.data_ptr(), self._gflat.data_ptr(), optimizer._m.data_ptr(),
-                optimizer._v.data_ptr(), self._bnflat.data_ptr(), self._nbt.data_ptr(), _lib.ptr(eps), seed, float(self.kld_weight),
-                n, offs, sizes, lrs, b1s, beta2, adam_eps, wd, float(optimizer.grad_scale), optimizer._step + 1, int(exchange),
-                xhat.data_ptr(), mu.data_ptr(), lv.data_ptr(), z.data_ptr(), out3.data_ptr(), self._stream()), "vae_train_step_fused")
+            if clip is not None:
+                _lib.check(_lib.lib().vae_train_step_fused_clipped(
+                    ctx.handle, x.data_ptr(), B, self._flat.data_ptr(), self._gflat.data_ptr(), optimizer._m.data_ptr(),
+                    optimizer._v.data_ptr(), self._bnflat.data_ptr(), self._nbt.data_ptr(), _lib.ptr(eps), seed, float(self.kld_weight),
+                    n, offs, sizes, lrs, b1s, beta2, adam_eps, wd, float(optimizer.grad_scale), *clip, int(exchange),
+                    xhat.data_ptr(), mu.data_ptr(), lv.data_ptr(), z.data_ptr(), out3.data_ptr(), self._stream()),
+                    "vae_train_step_fused_clipped")
+            else:
+                _lib.check(_lib.lib().vae_train_step_fused(
+                    ctx.handle, x.data_ptr(), B, self._flat.data_ptr(), self._gflat.data_ptr(), optimizer._m.data_ptr(),
+                    optimizer._v.data_ptr(), self._bnflat.data_ptr(), self._nbt.data_ptr(), _lib.ptr(eps), seed, float(self.kld_weight),
+                    n, offs, sizes, lrs, b1s, beta2, adam_eps, wd, float(optimizer.grad_scale), optimizer._step + 1, int(exchange),
+                    xhat.data_ptr(), mu.data_ptr(), lv.data_ptr(), z.data_ptr(), out3.data_ptr(), self._stream()), "vae_train_step_fused")
         optimizer._stepped()
         self._last = dict(x=x, xhat=xhat, mu=mu, lv=lv, z=z, train=True, B=B)
         params, views = self._param_grad_views()

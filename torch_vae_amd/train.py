@@ -27,7 +27,11 @@ BASE_BATCH_SIZE = 128  # train.py: lr_relative is quoted per 128 samples
 
 def build_optimizer(config, model, steps_per_epoch: int):
     """train.py:201-238: lr = lr_relative * batch_size / 128; AdamW over the encoder and decoder
-    groups only (fc_mu, fc_var, decoder_input, final_layer are never updated); OneCycleLR."""
+    groups only (fc_mu, fc_var, decoder_input, final_layer are never updated); OneCycleLR.  ``config.max_grad_norm`` /
+    ``config.skip_nonfinite`` (optional) become FusedAdamW's device-side clipping / skipping; with a torch optimiser
+    train_one_epoch clips through torch.nn.utils.clip_grad_norm_, and skipping is not available."""
+    max_grad_norm = getattr(config, "max_grad_norm", None)
+    skip_nonfinite = bool(getattr(config, "skip_nonfinite", False))
     world = int(getattr(config, "world_size", 1))
     config.batch_size = config.batch_size_per_gpu * world
     config.lr = config.lr_relative * config.batch_size / BASE_BATCH_SIZE
@@ -39,8 +43,12 @@ def build_optimizer(config, model, steps_per_epoch: int):
                    "name": "decoder"})
     name = getattr(config, "optimizer", "AdamW")
     if name == "AdamW" and isinstance(model, VanillaVAE):
-        optimizer = FusedAdamW(params, lr=config.lr, weight_decay=getattr(config, "weight_decay", 0.0))
+        optimizer = FusedAdamW(params, lr=config.lr, weight_decay=getattr(config, "weight_decay", 0.0),
+                               max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
     else:
+        if skip_nonfinite:
+            raise NotImplementedError(f"skip_nonfinite needs the fused optimiser (optimizer='AdamW' on a torch_vae_amd VanillaVAE), "
+                                      f"not torch.optim.{name}")
         optimizer = getattr(torch.optim, name)(params, lr=config.lr, weight_decay=getattr(config, "weight_decay", 0.0))
     if getattr(config, "scheduler", "OneCycle").lower() != "onecycle":
         raise NotImplementedError(f"Scheduler {config.scheduler} not supported.")
@@ -228,6 +236,11 @@ def train_one_epoch(config, model, optimizer, scheduler, criterion, dataloader, 
     world = _dp_world()
     fused = (isinstance(model, VanillaVAE) and isinstance(optimizer, FusedAdamW)
              and getattr(criterion, "__self__", None) is model and not getattr(config, "freeze_encoder", False))
+    # gradient clipping: FusedAdamW clips (and skips) inside its update; any other optimiser through torch's clip_grad_norm_
+    max_grad_norm = getattr(config, "max_grad_norm", None)
+    torch_clip = max_grad_norm is not None and not isinstance(optimizer, FusedAdamW)
+    fused_clip = isinstance(optimizer, FusedAdamW) and optimizer._clip_on
+    grad_norm = None
     n_batches = len(dataloader)
     in_flight = deque()   # pinned host batches a device kernel may still be reading, with the event that follows that kernel
     for batch_idx, (stimuli, y_true) in enumerate(dataloader):
@@ -260,9 +273,13 @@ def train_one_epoch(config, model, optimizer, scheduler, criterion, dataloader, 
             loss_output["loss"].backward()
             if isinstance(model, VanillaVAE):
                 allreduce_gradients(model, optimizer)
+            if torch_clip:
+                grad_norm = torch.nn.utils.clip_grad_norm_([p for g in optimizer.param_groups for p in g["params"]], max_grad_norm)
             optimizer.step()
             out3 = torch.stack([loss_output["loss"].detach(), loss_output["reconstruction_loss"].detach(),
                                 loss_output["kld_loss"].detach()])
+        if fused_clip:
+            grad_norm = optimizer.last_grad_norm
         scheduler.step()
         total_step += 1
         batch_size_all = batch_size_this_gpu * getattr(config, "world_size", world)
@@ -278,7 +295,10 @@ def train_one_epoch(config, model, optimizer, scheduler, criterion, dataloader, 
             loss_epoch_dev = torch.zeros((), dtype=torch.float64, device=out3.device)
         loss_epoch_dev.add_(out3[0])          # (float64 += float32 in one kernel: the operand is widened inside it)
         if (printing and rank0) or logging or first_verbose:
-            loss_batch, loss_recon, loss_kld = out3.tolist()  # one D2H sync for the three .item() of train.py:672-674
+            if logging and grad_norm is not None:   # (the norm in the same synchronisation)
+                loss_batch, loss_recon, loss_kld, grad_norm_value = torch.cat([out3.double(), grad_norm.reshape(1).double()]).tolist()
+            else:
+                loss_batch, loss_recon, loss_kld = out3.tolist()  # one D2H sync for the three .item() of train.py:672-674
         if first_verbose:
             print("stimuli.shape =", stimuli.shape)
             print("logits.shape  =", reconstruction.shape)
@@ -293,7 +313,7 @@ def train_one_epoch(config, model, optimizer, scheduler, criterion, dataloader, 
                     f" KL Weight: {model.kld_weight:.5f}",
                 )
         if logging:
-            wandb.log({
+            record = {
                 "training/stepwise/epoch": epoch,
                 "training/stepwise/epoch_progress": epoch - 1 + (batch_idx + 1) / n_batches,
                 "training/stepwise/n_samples_seen": n_samples_seen,
@@ -301,9 +321,14 @@ def train_one_epoch(config, model, optimizer, scheduler, criterion, dataloader, 
                 "training/stepwise/train/loss_recon": loss_recon,
                 "training/stepwise/train/loss_kld": loss_kld,
                 "training/stepwise/train/kld_weight": model.kld_weight,
-            }, step=total_step)
+            }
+            if grad_norm is not None:
+                record["training/stepwise/train/grad_norm"] = grad_norm_value
+            wandb.log(record, step=total_step)
     loss_epoch = float(loss_epoch_dev) if loss_epoch_dev is not None else 0.0   # the epoch's one unconditional synchronisation
     results = {"loss": loss_epoch / n_batches}
+    if fused_clip and optimizer.skip_nonfinite:
+        results["skipped_steps"] = int(optimizer.skipped_steps)
     return results, total_step, n_samples_seen
 
 
