@@ -47,7 +47,8 @@ int vae_abi_version(void);
  * 0.bias,1.weight,1.bias,3.weight,3.bias}; each keeps the reference's own element layout
  * (Conv2d [Cout,Cin,3,3], ConvTranspose2d [Cin,Cout,3,3], Linear [out,in]).
  * generalised=0: flattened_size = 1024 (models.py:33,36; img_size must be 32).
- * generalised=1: flattened_size = 256*(img_size/16)^2 (not reference behaviour). */
+ * generalised=1: flattened_size = 256*(img_size/16)^2 (not reference behaviour).
+ * latent_dim: 1..4096; every size in that range runs on every path, anything else is refused here. */
 int vae_param_layout(int img_size, int latent_dim, int generalised, int64_t* offsets /*[40]*/,
                      int64_t* sizes /*[40]*/, int64_t* total);
 /* BatchNorm running statistics: one f32 buffer, per layer running_mean[C] then running_var[C]. */

@@ -99,7 +99,8 @@ def profile_sequence(model, fn):
 DEC = ("decoder_input", "decoder", "final_layer")
 
 
-@pytest.mark.parametrize("H,L,B,gen", [(32, 16, 1, False), (32, 16, 5, False), (64, 16, 3, True)])
+@pytest.mark.parametrize("H,L,B,gen", [(32, 16, 1, False), (32, 16, 5, False), (64, 16, 3, True),
+                                       (32, 300, 3, False)])   # L >= 288: decin_wgrad_kernel, latent_dz over dense slabs, fc_dgrad passes
 def test_eval_backward_and_input_gradient_match_torch(H, L, B, gen):
     m = model_for(H, L, gen, "f32", "bce", seed=80 + B)
     m.kld_weight = 2.0
@@ -135,9 +136,9 @@ def test_eval_backward_and_input_gradient_match_torch(H, L, B, gen):
 
 
 @pytest.mark.parametrize("mode", ["eval", "train"])
-@pytest.mark.parametrize("H,B,gen", [(32, 3, False), (64, 7, True)])
-def test_decode_is_differentiable(mode, H, B, gen):
-    L = 16
+@pytest.mark.parametrize("H,B,gen,L", [(32, 3, False, 16), (64, 7, True, 16), (32, 5, False, 600)],
+                         ids=["32-3-False", "64-7-True", "32-5-False-L600"])   # (L 600: decin_fwd_kernel's two z passes, decin_wgrad_kernel)
+def test_decode_is_differentiable(mode, H, B, gen, L):
     m = model_for(H, L, gen, "f32", "bce", seed=90 + B)
     m.train(mode == "train")
     P, bufs, s = ref_state(m)

@@ -54,7 +54,10 @@ def _compare(out, ref, tag, slack=None):
 
 
 @pytest.mark.parametrize("N,L,S", [(1, 1, 1), (1, 128, 3), (7, 1, 3), (7, 10, 1), (7, 128, 3), (1000, 16, 3), (1000, 128, 1),
-                                   (4099, 1, 3), (4099, 10, 1), (4099, 16, 1)])
+                                   (4099, 1, 3), (4099, 10, 1), (4099, 16, 1),
+                                   # a partial second dimension tile of the dims kernel (65..127: tiles of 64), partial second and
+                                   # later dimension stages of the joint kernel (> 128: stages of 128), the largest latent size
+                                   (33, 65, 2), (130, 100, 1), (9, 129, 3), (70, 200, 1), (5, 4096, 2)])
 def test_synthetic_explicit_eps(N, L, S):
     mu, lv = synthetic_posteriors(N, L, 100 + N + L)
     eps = np.random.default_rng(N * L + S).standard_normal((S, N, L)).astype(np.float32)

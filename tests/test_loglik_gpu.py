@@ -109,7 +109,7 @@ def run(model, x, K, **kw):
 
 
 @pytest.mark.parametrize("recon", ["bce", "mse"])
-@pytest.mark.parametrize("H,L,B,gen", [(32, 16, 4, False), (64, 16, 3, True), (128, 16, 2, True)])
+@pytest.mark.parametrize("H,L,B,gen", [(32, 16, 4, False), (64, 16, 3, True), (128, 16, 2, True), (32, 1024, 3, False)])
 def test_f32_against_torch_f64(H, L, B, gen, recon):
     m = model_for(H, L, gen, "f32", recon)
     x = rolls(B, H, 62, recon)

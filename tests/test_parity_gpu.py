@@ -103,7 +103,9 @@ def test_f32_step0_matches_reference_fixture(name):
                                  # (npad 96 / 160 / 192: the dense kernel's N tiling) and sizes that are not a multiple of 4
                                  (32, 40, 3, False), (32, 48, 5, False), (32, 80, 3, False), (32, 96, 4, False), (64, 160, 2, True),
                                  (32, 10, 6, False), (64, 10, 2, True), (32, 1, 3, False), (32, 3, 9, False),
-                                 (32, 16, 256, False), (64, 16, 48, True)])
+                                 (32, 16, 256, False), (64, 16, 48, True),
+                                 # L >= 288: decoder_input's weight gradient on decin_wgrad_kernel (batch slices) + reduce
+                                 (32, 320, 130, False)])
 @pytest.mark.parametrize("dtype", ["f32", "bf16", "f16"])
 def test_every_tensor_against_oracle(cfg, dtype):
     """All gradients (full tensors) against the fp64 oracle, with non-trivial BN affine/bias values,
@@ -399,6 +401,47 @@ def test_train_one_epoch_matches_reference_loop():
         del os.environ["VAE_ONE_CALL_STEP"]
     assert res2["loss"] == res["loss"]
     assert torch.equal(model2.flat_parameters(), model.flat_parameters())
+
+
+def test_train_one_epoch_ragged_last_batch_matches_oracle():
+    """train_one_epoch over a loader whose last batch is smaller (8, 8, 8, 5): the model keeps its context for 8 and runs the last
+    step in it.  Losses, parameters and BatchNorm running statistics against oracle.vae_oracle.Trainer (f64) stepped over the same
+    batches, at test_f32_training_trajectory's tolerances."""
+    from argparse import Namespace
+    from torch_vae_amd.train import build_optimizer, train_one_epoch
+    H, L, gen, sizes = 32, 16, False, (8, 8, 8, 5)
+    model = make_model(H, L, gen, "f32", vo.init_params(L, H, 7, gen))
+    cfg = Namespace(batch_size_per_gpu=8, world_size=1, lr_relative=0.01, weight_decay=0.0, optimizer="AdamW", scheduler="OneCycle",
+                    epochs=1, log_wandb=False, print_interval=1000, log_interval=1000, freeze_encoder=False, global_rank=0)
+    opt, sched = build_optimizer(cfg, model, steps_per_epoch=len(sizes))
+    xs = [vo.synth_pianoroll(b, H, 300 + s) for s, b in enumerate(sizes)]
+    epss = [vo.counter_normal(b * L, 300 + s, 5).reshape(b, L) for s, b in enumerate(sizes)]
+    it, losses = iter(epss), []
+    orig = model.fused_train_step
+
+    def step(o, x, **k):      # (the loop steps through VanillaVAE.fused_train_step: the oracle's noise is injected there)
+        out3, xhat = orig(o, x, **{**k, "eps": torch.from_numpy(next(it)).float().cuda()})
+        losses.append(out3.tolist())
+        return out3, xhat
+    model.fused_train_step = step
+    loader = [(torch.from_numpy(x), torch.zeros(x.shape[0], dtype=torch.long)) for x in xs]
+    _, total_step, n_seen = train_one_epoch(cfg, model, opt, sched, model.loss, loader, device="cuda", epoch=1)
+    assert total_step == len(sizes) and n_seen == sum(sizes) and model._ctx.key[2] == 8
+    tr = vo.make_trainer(L, H, 8, len(sizes), seed=7, generalised=gen)
+    want = []
+    for x, eps in zip(xs, epss):
+        lo, _, _ = tr.step(x.astype(np.float64), eps)
+        want.append([float(lo["loss"]), float(lo["reconstruction_loss"]), float(lo["kld_loss"])])
+    np.testing.assert_allclose(np.array(losses), np.array(want), rtol=3e-4)
+    sd = model.state_dict()
+    for k, v in tr.bn_state.items():
+        if k.endswith("num_batches_tracked"):
+            assert int(sd[k]) == int(v) == len(sizes), k
+        else:
+            np.testing.assert_allclose(sd[k].cpu().numpy(), v, rtol=1e-3, atol=1e-5, err_msg=k)
+    for k, v in tr.p.items():
+        if k not in PRE_BN_BIAS:
+            np.testing.assert_allclose(np.sqrt((sd[k].double().cpu().numpy() ** 2).sum()), np.sqrt((v ** 2).sum()), rtol=1e-3, err_msg=k)
 
 
 def test_train_one_epoch_byte_stimuli_match_float_stimuli():
@@ -1483,21 +1526,32 @@ def test_streaming_output_conv_matches_tiled_kernel(dtype, B, bands):
     assert max(worst[n] for n in ("final_layer.3.weight", "final_layer.3.bias", "final_layer.1.weight", "final_layer.1.bias")) < 1e-5, worst
 
 
-def _layer_local_gaps(dtype, H, L, B, gen, seed=41, opts=None, kld_weight=1.0, exact_convout=False):
+def _layer_local_gaps(dtype, H, L, B, gen, seed=41, opts=None, kld_weight=1.0, exact_convout=False, warm=None, keep=None):
     """Every 16-bit kernel of the step against the storage-emulating oracle ON THE KERNEL'S OWN INPUTS: each stored tensor (y_l, dz_l,
     decoder_input's output and gradient) and each parameter gradient is recomputed on the CPU from the tensors the GPU actually
     stored one layer earlier, so a gap is that one kernel's, not the chain's.  (The end-to-end emulation of
     test_every_tensor_against_oracle cannot be tighter than the chain allows: 1-ulp differences in stored activations flip
-    LeakyReLU slopes a few layers later - DESIGN.md section 4.)  Returns {tensor name: relative L2 gap}."""
+    LeakyReLU slopes a few layers later - DESIGN.md section 4.)  Returns {tensor name: relative L2 gap}.
+    warm: batch size of a step run first on the same model, so that the checked step runs in a context sized for that larger batch
+    (a model keeps one context for the largest batch it has seen: train_one_epoch's ragged last batch).  keep: a dict that receives
+    the checked step's ELBO scalars and flat gradient."""
     from torch_vae_amd import _lib
     p = perturbed_params(L, H, seed, gen)
     x = vo.synth_pianoroll(B, H, 21).astype(np.float64)
     eps = vo.counter_normal(B * L, 21, 5).reshape(B, L).astype(np.float64)
     m = make_model(H, L, gen, dtype, p, kld_weight=kld_weight)
     for k, v in (opts or {}).items():
-        _lib.check(_lib.lib().vae_set_option(m._context(B).handle, k.encode(), v), "set " + k)
-    m.fused_forward_backward(torch.from_numpy(x).float().cuda(), eps=torch.from_numpy(eps).float().cuda())
+        _lib.check(_lib.lib().vae_set_option(m._context(max(B, warm or 0)).handle, k.encode(), v), "set " + k)
+    if warm:
+        assert warm > B
+        xw = torch.from_numpy(vo.synth_pianoroll(warm, H, 22)).cuda()
+        m.fused_forward_backward(xw, eps=torch.from_numpy(vo.counter_normal(warm * L, 22, 5).reshape(warm, L)).float().cuda())
+    out3, _ = m.fused_forward_backward(torch.from_numpy(x).float().cuda(), eps=torch.from_numpy(eps).float().cuda())
     torch.cuda.synchronize()
+    if warm:
+        assert m._ctx.key[2] == warm
+    if keep is not None:
+        keep["out3"], keep["grads"] = out3.clone(), m.flat_grads().clone()
     grads = flat_grad_dict(m)
     last = {k: m._last[k].double().cpu().numpy() for k in ("xhat", "mu", "lv", "z")}
     C = [32, 64, 128, 256, 128, 64, 32, 32]
@@ -1593,13 +1647,30 @@ def _layer_local_gaps(dtype, H, L, B, gen, seed=41, opts=None, kld_weight=1.0, e
     return gaps
 
 
+# Latent sizes on each side of every switch of the latent block (vae_impl.cuh, backward_second; defaults of vae_ctx.h):
+#   L <= 64   fc input gradient on fc_dgrad8_kernel (16-bit), else fc_dgrad_kernel
+#   L <= 144  fc weight gradient on batch_gemm_kernel (2L <= 288), else fc_wgrad_kernel + reduce
+#   L <= 287  decoder_input weight gradient on batch_gemm_kernel (L + 1 <= 288), else decin_wgrad_kernel + reduce
+#   L > 256   fc_dgrad_kernel stages its dlat rows in more than one LDS pass (FC_DGRAD_JC); L > 512 decin_fwd_kernel its z rows (DECIN_LC)
+# up to the largest latent size the library accepts, in all three kernel modes at small ragged batches, and once at a batch of 130
+# (decin_wgrad_kernel's batch slices: 7 x 17 + 11).
+LATENT_SWEEP = [(d, 32, L, B, False) for d in ("bf16", "f16", "f32")
+                for L, B in ((129, 5), (144, 3), (145, 7), (287, 3), (288, 5), (1024, 3), (4096, 2))] + [("bf16", 32, 320, 130, False)]
+# Batches and latent sizes where the 16-bit kernels' tiles are partial: one image at every image size, two images, ragged batches of
+# 33 / 130 (32x32) and 48 (64x64), latent sizes 1, 3 and 40
+EDGE_BATCHES = [(d, H, L, B, gen) for d in ("bf16", "f16")
+                for H, L, B, gen in ((32, 16, 1, False), (128, 16, 1, True), (256, 16, 1, True), (64, 16, 2, True), (32, 16, 33, False),
+                                     (32, 16, 130, False), (64, 16, 48, True), (32, 1, 3, False), (32, 3, 9, False), (32, 40, 6, False))]
+
+
 @pytest.mark.parametrize("dtype,H,L,B,gen", [("f32", 32, 16, 6, False), ("f32", 64, 16, 5, True), ("f32", 128, 16, 3, True),
                                              ("bf16", 32, 16, 6, False), ("f16", 32, 16, 6, False), ("bf16", 32, 10, 7, False),
                                              ("bf16", 64, 16, 5, True), ("f16", 64, 128, 4, True), ("bf16", 128, 16, 3, True),
                                              ("f16", 128, 16, 3, True), ("bf16", 128, 16, 9, True), ("f16", 128, 64, 8, True),
                                              # BASELINE configs[1] and configs[4] (per GPU) at full size; configs[2]'s model at batch 64
                                              ("bf16", 128, 16, 256, True), ("f16", 128, 128, 512 if FULL_TESTS else 64, True),
-                                             ("bf16", 256, 64, 64 if FULL_TESTS else 16, True)])
+                                             ("bf16", 256, 64, 64 if FULL_TESTS else 16, True)]
+                         + LATENT_SWEEP + EDGE_BATCHES)
 def test_every_kernel_against_oracle_on_its_own_inputs(dtype, H, L, B, gen):
     """Layer-local parity of the 16-bit modes (see _layer_local_gaps): 54 tensors per case - every stored activation and gradient,
     the latent block, xhat and every parameter gradient - each within 5e-4 (relative L2) of the storage-emulating oracle evaluated
@@ -1647,6 +1718,41 @@ def test_every_kernel_variant_against_oracle_on_its_own_inputs(vi):
         report(test="layer_local_variant", opts=opts, dtype=dtype, img=H, worst=worst, worst_gap=gaps[worst])
         bad = {k: v for k, v in gaps.items() if not v < 5e-4}
         assert not bad, (opts, dtype, bad)
+
+
+# variants whose tiling differs from the defaults' (the tiled forms of the streaming kernels, the separate and the 8-wave weight
+# gradients, the latent block on the MFMA / VALU kernels, one-tile-per-workgroup convs), at one image of 128x128 and a ragged 33 of 64x64
+EDGE_VARIANTS = [0, 2, 5, 7, 8, 9, 11, 12, 18]
+
+
+@pytest.mark.parametrize("dtype,H,B", [("bf16", 128, 1), ("f16", 64, 33)])
+@pytest.mark.parametrize("vi", EDGE_VARIANTS, ids=["+".join(f"{k}={v}" for k, v in KERNEL_VARIANTS[i].items()) for i in EDGE_VARIANTS])
+def test_kernel_variants_at_edge_batches(vi, dtype, H, B):
+    """test_every_kernel_variant_against_oracle_on_its_own_inputs at a batch of one image and at a ragged batch of 33."""
+    opts = KERNEL_VARIANTS[vi]
+    gaps = _layer_local_gaps(dtype, H, 16, B, True, seed=45, opts=opts, exact_convout=opts.get("use_mfma_convout", 1) == 0)
+    worst = max(gaps, key=gaps.get)
+    report(test="layer_local_variant_edge", opts=opts, dtype=dtype, img=H, batch=B, worst=worst, worst_gap=gaps[worst])
+    bad = {k: v for k, v in gaps.items() if not v < 5e-4}
+    assert not bad, (opts, dtype, bad)
+
+
+@pytest.mark.parametrize("dtype,H,L,B,warm,gen", [("bf16", 32, 16, 3, 40, False), ("f16", 32, 16, 3, 40, False), ("f32", 32, 16, 3, 40, False),
+                                                  ("bf16", 64, 16, 1, 9, True), ("f16", 128, 16, 1, 9, True), ("bf16", 32, 320, 5, 33, False)])
+def test_smaller_batch_on_a_context_sized_for_a_larger_one(dtype, H, L, B, warm, gen):
+    """A step at batch B on a model whose context was sized by an earlier step at a larger batch (the launch plans are re-derived
+    from the batch of each call): every kernel within the layer-local gate, and the ELBO scalars and every gradient bit-identical to
+    the same step on a fresh model."""
+    keep, fresh = {}, {}
+    gaps = _layer_local_gaps(dtype, H, L, B, gen, seed=49, warm=warm, keep=keep)
+    worst = max(gaps, key=gaps.get)
+    report(test="layer_local_reused_context", dtype=dtype, img=H, latent=L, batch=B, warm=warm, worst=worst, worst_gap=gaps[worst])
+    gate = 1e-5 if dtype == "f32" else 5e-4
+    bad = {k: v for k, v in gaps.items() if not v < gate}
+    assert not bad, bad
+    _layer_local_gaps(dtype, H, L, B, gen, seed=49, keep=fresh)
+    assert torch.equal(keep["out3"], fresh["out3"]), (keep["out3"], fresh["out3"])
+    assert torch.equal(keep["grads"], fresh["grads"])
 
 
 @pytest.mark.parametrize("dtype,H,L,B,gen", [("f32", 64, 16, 5, True), ("bf16", 32, 16, 6, False), ("f16", 64, 16, 5, True),

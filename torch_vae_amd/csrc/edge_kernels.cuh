@@ -540,10 +540,14 @@ template <typename T> struct FcDgradArgs {
     int bt_per_wg;   // batch rows per workgroup (multiple of 16)
     float gmul;      // scale of gpre (f16 gradient scaling; 1 otherwise)
 };
+// dlat columns staged in LDS per pass (32 KiB): larger latents take several passes over the same sequential j chain, so the
+// sums are the same for every latent size and the LDS need does not grow with it
+constexpr int FC_DGRAD_JC = 512;
+static inline size_t fc_dgrad_lds(int L2) { return (size_t)std::min(L2, FC_DGRAD_JC) * 16 * 4; }
 template <typename T>
 __global__ __launch_bounds__(256) void fc_dgrad_kernel(FcDgradArgs<T> a) {
     constexpr int BT = 16;
-    extern __shared__ __attribute__((aligned(16))) float dl_s[];  // [L2][BT]
+    extern __shared__ __attribute__((aligned(16))) float dl_s[];  // [min(L2, FC_DGRAD_JC)][BT]
     const int tid = threadIdx.x, fp = blockIdx.x * 256 + tid;
     const int c = fp & 255;
     const float sc = a.ocoef[LC_SC * 256 + c], sh = a.ocoef[LC_SH * 256 + c];
@@ -552,25 +556,28 @@ __global__ __launch_bounds__(256) void fc_dgrad_kernel(FcDgradArgs<T> a) {
     float s1 = 0.f, s2 = 0.f;
     const int bend = min(a.B, (int)(blockIdx.y + 1) * a.bt_per_wg);
     for (int b0 = blockIdx.y * a.bt_per_wg; b0 < bend; b0 += BT) {
-        __syncthreads();
-        for (int i = tid; i < a.L2 * BT; i += 256) {
-            const int j = i / BT, bb = i % BT;
-            dl_s[i] = (b0 + bb < a.B) ? a.dlat[(size_t)(b0 + bb) * a.L2 + j] : 0.f;
-        }
-        __syncthreads();
         float yv[BT], acc[BT];
 #pragma unroll
         for (int bb = 0; bb < BT; ++bb) {   // y rows in flight while the dot products run
             acc[bb] = 0.f;
             yv[bb] = (b0 + bb < a.B) ? tofloat(a.y[(size_t)(b0 + bb) * a.F + fp]) : 0.f;
         }
-        for (int j = 0; j < a.L2; ++j) {
-            const float w = tofloat(wrow[(size_t)j * 8]);
+        for (int j0 = 0; j0 < a.L2; j0 += FC_DGRAD_JC) {
+            const int nj = min(FC_DGRAD_JC, a.L2 - j0);
+            __syncthreads();
+            for (int i = tid; i < nj * BT; i += 256) {
+                const int j = i / BT, bb = i % BT;
+                dl_s[i] = (b0 + bb < a.B) ? a.dlat[(size_t)(b0 + bb) * a.L2 + j0 + j] : 0.f;
+            }
+            __syncthreads();
+            for (int j = 0; j < nj; ++j) {
+                const float w = tofloat(wrow[(size_t)(j0 + j) * 8]);
 #pragma unroll
-            for (int q = 0; q < BT / 4; ++q) {
-                const f32x4 d = *reinterpret_cast<const f32x4*>(&dl_s[j * BT + q * 4]);
+                for (int q = 0; q < BT / 4; ++q) {
+                    const f32x4 d = *reinterpret_cast<const f32x4*>(&dl_s[j * BT + q * 4]);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) acc[q * 4 + e] += d[e] * w;
+                    for (int e = 0; e < 4; ++e) acc[q * 4 + e] += d[e] * w;
+                }
             }
         }
 #pragma unroll
@@ -733,33 +740,44 @@ __global__ __launch_bounds__(256) void fc_wgrad_kernel(FcWgradArgs<T> a) {
 }
 
 // decoder_input forward (models.py:162): d0[b][f'] = bd[f] + sum_l z[b][l] Wd[f][l]
+// latent columns staged in LDS per pass (32 KiB; a multiple of 4, so the 16-byte path keeps its grouping): larger latents take
+// several passes over the same sequential l chain, so the sums are the same for every latent size
+constexpr int DECIN_LC = 512;
+static inline size_t decin_fwd_lds(int L) { return (size_t)16 * std::min(L, DECIN_LC) * 4; }
 template <typename T>
 __global__ __launch_bounds__(256) void decin_fwd_kernel(const float* __restrict__ z, const float* __restrict__ wd,
                                                         const float* __restrict__ bd, T* __restrict__ d0, int B, int F, int L, int s2) {
     constexpr int BT = 16;
-    extern __shared__ __attribute__((aligned(16))) float z_s[];  // [BT][L]
+    extern __shared__ __attribute__((aligned(16))) float z_s[];  // [BT][min(L, DECIN_LC)]
     const int tid = threadIdx.x, fp = blockIdx.x * 256 + tid, b0 = blockIdx.y * BT, fr = fref_of(fp, s2);
-    for (int i = tid; i < BT * L; i += 256) z_s[i] = (b0 + i / L < B) ? z[(size_t)b0 * L + i] : 0.f;
-    __syncthreads();
     float acc[BT];
     const float bias = bd[fr];
 #pragma unroll
     for (int bb = 0; bb < BT; ++bb) acc[bb] = bias;
     const float* wrow = wd + (size_t)fr * L;
-    if ((L & 3) == 0) {
-        for (int l = 0; l < L; l += 4) {
-            const f32x4 w = *reinterpret_cast<const f32x4*>(wrow + l);
-#pragma unroll
-            for (int bb = 0; bb < BT; ++bb) {
-                const f32x4 zz = *reinterpret_cast<const f32x4*>(&z_s[bb * L + l]);
-                acc[bb] += zz[0] * w[0] + zz[1] * w[1] + zz[2] * w[2] + zz[3] * w[3];
-            }
+    for (int l0 = 0; l0 < L; l0 += DECIN_LC) {
+        const int nl = min(DECIN_LC, L - l0);
+        if (l0) __syncthreads();
+        for (int i = tid; i < BT * nl; i += 256) {
+            const int bb = i / nl, l = i - bb * nl;
+            z_s[i] = (b0 + bb < B) ? z[(size_t)(b0 + bb) * L + l0 + l] : 0.f;
         }
-    } else {   // latent sizes that are not a multiple of 4 (the reference's default is 10): rows are not 16-byte aligned
-        for (int l = 0; l < L; ++l) {
-            const float w = wrow[l];
+        __syncthreads();
+        if ((L & 3) == 0) {
+            for (int l = 0; l < nl; l += 4) {
+                const f32x4 w = *reinterpret_cast<const f32x4*>(wrow + l0 + l);
 #pragma unroll
-            for (int bb = 0; bb < BT; ++bb) acc[bb] += z_s[bb * L + l] * w;
+                for (int bb = 0; bb < BT; ++bb) {
+                    const f32x4 zz = *reinterpret_cast<const f32x4*>(&z_s[bb * nl + l]);
+                    acc[bb] += zz[0] * w[0] + zz[1] * w[1] + zz[2] * w[2] + zz[3] * w[3];
+                }
+            }
+        } else {   // latent sizes that are not a multiple of 4 (the reference's default is 10): rows are not 16-byte aligned
+            for (int l = 0; l < nl; ++l) {
+                const float w = wrow[l0 + l];
+#pragma unroll
+                for (int bb = 0; bb < BT; ++bb) acc[bb] += z_s[bb * nl + l] * w;
+            }
         }
     }
 #pragma unroll

@@ -509,7 +509,9 @@ int decode_impl(vae_ctx* c, const float* z, int B, const float* params, float* b
     } else {
         dim3 grid((unsigned)(c->F / 256), (B + 15) / 16);
         ProfScope ps(c, "decin_fwd", (double)sizeof(T) * B * (double)c->F + 4.0 * c->F * L, 2.0 * B * c->F * L, st);
-        hipLaunchKernelGGL((decin_fwd_kernel<T>), grid, dim3(256), 16 * L * 4, st, z, params + c->poff[20], params + c->poff[21],
+        const size_t lds = decin_fwd_lds(L);
+        if (set_lds(decin_fwd_kernel<T>, lds)) return -1;
+        hipLaunchKernelGGL((decin_fwd_kernel<T>), grid, dim3(256), lds, st, z, params + c->poff[20], params + c->poff[21],
                            reinterpret_cast<T*>(c->d0), B, (int)c->F, L, c->s2);
         LAUNCH_CHECK("decin_fwd_kernel");
     }
@@ -1047,13 +1049,19 @@ static int backward_second(vae_ctx* c, const float* x, const float* params, floa
                 const bool big = (c->use_fc_dgrad8 & 2) && B > 32;
                 d.bt_per_wg = big ? std::max(64, ((B + 3) / 4 + 63) / 64 * 64) : (d.bt_per_wg + 31) / 32 * 32;
                 const dim3 grid((unsigned)(c->F / 256), (B + d.bt_per_wg - 1) / d.bt_per_wg);
-                if (big) hipLaunchKernelGGL((fc_dgrad8_kernel<T, 4, 16>), grid, dim3(512), fc_dgrad8_lds(2 * L, 4, 16), st, d);
-                else hipLaunchKernelGGL((fc_dgrad8_kernel<T, 4, 8>), grid, dim3(256), fc_dgrad8_lds(2 * L, 4, 8), st, d);
+                if (big) {
+                    if (set_lds(fc_dgrad8_kernel<T, 4, 16>, fc_dgrad8_lds(2 * L, 4, 16))) return -1;
+                    hipLaunchKernelGGL((fc_dgrad8_kernel<T, 4, 16>), grid, dim3(512), fc_dgrad8_lds(2 * L, 4, 16), st, d);
+                } else {
+                    if (set_lds(fc_dgrad8_kernel<T, 4, 8>, fc_dgrad8_lds(2 * L, 4, 8))) return -1;
+                    hipLaunchKernelGGL((fc_dgrad8_kernel<T, 4, 8>), grid, dim3(256), fc_dgrad8_lds(2 * L, 4, 8), st, d);
+                }
                 LAUNCH_CHECK("fc_dgrad8_kernel");
             }
         }
         if (!wide) {
-            hipLaunchKernelGGL((fc_dgrad_kernel<T>), dim3((unsigned)(c->F / 256), (B + d.bt_per_wg - 1) / d.bt_per_wg), dim3(256), 2 * L * 16 * 4, st, d);
+            if (set_lds(fc_dgrad_kernel<T>, fc_dgrad_lds(2 * L))) return -1;
+            hipLaunchKernelGGL((fc_dgrad_kernel<T>), dim3((unsigned)(c->F / 256), (B + d.bt_per_wg - 1) / d.bt_per_wg), dim3(256), fc_dgrad_lds(2 * L), st, d);
             LAUNCH_CHECK("fc_dgrad_kernel");
         }
     }
