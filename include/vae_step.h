@@ -129,6 +129,33 @@ int vae_elbo_generic_ex(const float* xhat, const float* target, const float* mu,
                         int batch, int latent_dim, float kld_weight, int recon, float* out3, float* g_xhat,
                         float* g_mu, float* g_log_var, vae_stream_t stream);
 
+/* KL objective of the ELBO: T replaces KL in loss = reconstruction_loss + kld_weight * T.  All in nats, from the forward's f32
+ * mu / log_var [B,L]:  kl_d = 1/B sum_b -0.5 (1 + log_var_bd - mu_bd^2 - exp(log_var_bd)),  KL = sum_d kl_d (models.py:214).
+ *   VAE_KL_PLAIN      T = KL (default, the reference's)
+ *   VAE_KL_FREE_BITS  T = sum_d max(kl_d, param), param = lambda > 0 nats per dimension (Kingma et al. 2016): a dimension whose
+ *                     batch-mean KL is not above lambda gets no KL gradient (torch.clamp(kl_d, min=lambda).sum() under autograd)
+ *   VAE_KL_CAPACITY   T = |KL - param|, param = C >= 0 nats (Burgess et al. 2018; kld_weight plays gamma): the KL gradient is
+ *                     multiplied by sign(KL - C), 0 at equality
+ * kl_d, KL and T are reduced in f64 in a fixed order by one extra launch per forward (none for VAE_KL_PLAIN), so the mask / sign
+ * decision is the same bits on every run; it stays on the device.  out3 keeps its meaning: kld_loss is the raw KL with the
+ * reference's flipped sign whatever the objective (T = (loss - reconstruction_loss) / kld_weight).  The batch is the one this
+ * context sees: data-parallel replicas decide on their own batch means.  vae_log_likelihood / vae_latent_stats are unaffected. */
+#define VAE_KL_PLAIN 0
+#define VAE_KL_FREE_BITS 1
+#define VAE_KL_CAPACITY 2
+/* KL objective for the following forwards of this context (sticky; default plain).  A forward records kind and param: its loss,
+ * deferred loss and backward (vae_backward, _part, _ex with use_std = 1, the training steps) use the recorded ones even if the
+ * setting changes after.  A NaN, negative or infinite param, or VAE_KL_FREE_BITS with param <= 0, returns -1.  Enqueues nothing:
+ * a per-step capacity ramp may call it every step. */
+int vae_set_kl_objective(vae_ctx* ctx, int kind, double param);
+/* vae_elbo_generic_ex with the KL objective chosen per call: g_mu / g_log_var are the gradients of kld_weight * T. */
+int vae_elbo_generic_kl(const float* xhat, const float* target, const float* mu, const float* log_var, int64_t n,
+                        int batch, int latent_dim, float kld_weight, int recon, int kl_kind, double kl_param, float* out3,
+                        float* g_xhat, float* g_mu, float* g_log_var, vae_stream_t stream);
+/* kl_d [latent_dim] f64 of the last forward (vae_forward, the training steps, vae_encode), device memory, no host
+ * synchronisation: the forward's own reduction when it ran with an objective other than plain, else reduced on demand. */
+int vae_kl_per_dim(vae_ctx* ctx, double* out, vae_stream_t stream);
+
 /* Importance-weighted log-likelihood (IWAE_K) and per-sample ELBO of x under the model in eval mode.
  * eps [K,B,L] f32 or NULL (device counter generator, seed, stream 6; index (k*B+b)*L+l).
  * Decodes `chunk` draws of the whole batch per pass: chunk*batch <= max_batch.
@@ -306,7 +333,9 @@ int vae_profile_timeline(vae_ctx* ctx, char* buf, int64_t capacity);
 int vae_debug_stamps(vae_ctx* ctx, const char* tag, int epi, long long* out);
 
 /* Debug / test hooks: copy an internal NHWC tensor to f32 NCHW.  which: 0..7 raw conv output
- * of BN layer i, 8..15 its dz, 16 decoder_input output, 17 its gradient. */
+ * of BN layer i, 8..15 its dz, 16 decoder_input output, 17 its gradient; 18 the latent gradient of the last backward,
+ * [B, 2 latent_dim] f32 (dmu | dlog_var per row, times the f16 gradient scale), and 19 the per-dimension factors [latent_dim] f32 of the last
+ * forward's KL objective (an error after a plain forward), both copied as they are. */
 int vae_debug_tensor(vae_ctx* ctx, int which, float* out, int64_t capacity, vae_stream_t stream);
 /* hardware self-test of the transposed LDS read used by the bf16 weight-gradient kernel */
 int vae_selftest_tr16(vae_stream_t stream);

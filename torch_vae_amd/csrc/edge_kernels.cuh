@@ -440,23 +440,29 @@ static __global__ void latent_fwd_kernel(LatentFwdArgs a) {
 
 // ELBO scalars (models.py:216-225): loss = bce + kld_weight*kld ; kld_loss reported with flipped sign.
 // nrep: replicas of the accumulator block (STAT_R for a context's accumulators, 1 for the generic-loss buffer)
-static __global__ void loss_finalize_kernel(const double* accum, float* out3, double inv_n, double inv_b, float kld_weight, int nrep) {
+// shaped: null for the plain objective; else kl_shape_kernel's scalars, shaped[0] = T (free bits / capacity term, f64) replaces KL
+// in the loss - kld_loss stays the raw KL, so logs compare across objectives
+static __global__ void loss_finalize_kernel(const double* accum, float* out3, double inv_n, double inv_b, float kld_weight, int nrep,
+                                            const double* shaped = nullptr) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         double a0 = 0.0, a1 = 0.0;
         for (int rep = 0; rep < nrep; ++rep) { a0 += accum[rep * 8 + 0]; a1 += accum[rep * 8 + 1]; }
         const double bce = a0 * inv_n, kld = -0.5 * a1 * inv_b;
-        out3[0] = (float)(bce + (double)kld_weight * kld); out3[1] = (float)bce; out3[2] = (float)(-kld);
+        out3[0] = (float)(bce + (double)kld_weight * (shaped ? shaped[0] : kld)); out3[1] = (float)bce; out3[2] = (float)(-kld);
     }
 }
-static __global__ void kld_only_kernel(const float* mu, const float* lv, double* accum, int n, float k, float* gmu, float* glv) {
+// factor [L]: per-dimension factor of the KL objective (kl_shape_kernel), null = plain (1)
+static __global__ void kld_only_kernel(const float* mu, const float* lv, double* accum, int n, float k, float* gmu, float* glv,
+                                       const float* factor = nullptr, int L = 1) {
     __shared__ float wred[4];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     float term = 0.f;
     if (i < n) {
         const float m = mu[i], v = lv[i], ev = expf(v);
         term = 1.f + v - m * m - ev;
-        if (gmu) gmu[i] = k * m;                  // d(kld_weight*KL)/dmu
-        if (glv) glv[i] = k * 0.5f * (ev - 1.f);  // d(kld_weight*KL)/dlog_var
+        if (factor) k *= factor[i % L];           // 0 / +-1: exact
+        if (gmu) gmu[i] = k * m;                  // d(kld_weight*T)/dmu
+        if (glv) glv[i] = k * 0.5f * (ev - 1.f);  // d(kld_weight*T)/dlog_var
     }
     term = wave_sum(term);
     if ((threadIdx.x & 63) == 0) wred[threadIdx.x >> 6] = term;
@@ -471,7 +477,12 @@ struct LatentBwdArgs {
     float* dlat;                          // [B][2L]: dmu | dlv
     int B, L; float kld_weight; int add_kl;
     float gmul;                           // every upstream gradient entering here is multiplied by it (f16 gradient scaling; 1 otherwise)
+    const float* factor;                  // SHAPED only: per-dimension factor of the KL objective [L] (kl_shape_kernel)
 };
+// SHAPED: the KL contribution of dimension l is multiplied by factor[l] (free bits: 0 below the floor, capacity: sign(KL - C)).
+// The factor is 0 or +-1, so it changes no magnitude: the power-of-two gradient scaling of f16 storage (gmul / ginv) is untouched.
+// The plain objective launches the SHAPED = false instantiation, whose code is what it was before the objectives existed.
+template <bool SHAPED>
 static __global__ void latent_bwd_kernel(LatentBwdArgs a) {   // LAT_LANES lanes per (b,l)
     const int i = (blockIdx.x * blockDim.x + threadIdx.x) / LAT_LANES, sub = threadIdx.x & (LAT_LANES - 1);
     const bool ok = i < a.B * a.L;
@@ -491,7 +502,8 @@ static __global__ void latent_bwd_kernel(LatentBwdArgs a) {   // LAT_LANES lanes
     const float m = a.mu[i], v = a.lv[i], sd = expf(0.5f * v);
     float dmu = d, dlv = d * a.eps[i] * sd * 0.5f;
     if (a.add_kl) {
-        const float k = gs * a.kld_weight / (float)a.B;
+        float k = gs * a.kld_weight / (float)a.B;
+        if constexpr (SHAPED) k *= a.factor[l];
         dmu += k * m; dlv += k * 0.5f * (expf(v) - 1.f);
     }
     if (a.gmu) dmu += a.gmu[i] * a.gmul;
@@ -505,6 +517,103 @@ static __global__ void colsum_kernel(const float* __restrict__ m, int rows, int 
     for (int r = threadIdx.x; r < rows; r += 64) s += m[(size_t)r * cols + j];
     s = wave_sum(s) * scale;
     if (threadIdx.x == 0) { if (j < split) o0[j] = s; else o1[j - split] = s; }
+}
+
+// ---------------------------------------------------------------------------
+// KL objectives (free bits, capacity target): the batch reduction the backward and the ELBO scalars need, in f64 and in a fixed
+// order, so that the mask / sign decision is the same bits on every run.  From the forward's f32 mu / log_var [B][L]:
+//   kl_bd = -0.5 (1 + lv - mu^2 - exp(lv))  (f64, f64 exp),   kl_d = 1/B sum_b kl_bd,   KL = sum_d kl_d
+//   plain:      factor_d = 1,                      T = KL
+//   free bits:  factor_d = kl_d > lambda ? 1 : 0,  T = sum_d max(kl_d, lambda)        (torch.clamp(kl_d, min=lambda).sum())
+//   capacity:   factor_d = sign(KL - C),           T = |KL - C|                       ((KL - C).abs(); 0 at equality)
+// One workgroup per VEC columns (VEC = 4: 16-byte loads, when L % 4 == 0 and the rows are 16-byte aligned; else 1).  Thread t
+// sums rows t, t + 256, ... in order, the 256 partial sums meet in a fixed tree: no atomic accumulation anywhere, and the two
+// VEC forms add every column in the same order.  The sums over dimensions belong to the LAST ARRIVING workgroup: each
+// workgroup stores its kl_d write-through (agent scope), drains, releases and takes a ticket; the one that draws the last
+// ticket acquires and adds the stored kl_d, thread t taking d = t, t + 256, ... in order and the same tree on top - whichever
+// workgroup that is, it adds the same numbers in the same order.  ticket: one zeroed word per launch.
+struct KlShapeArgs {
+    const float* mu; const float* lv;
+    unsigned long long* kl_d;   // [L] f64 bit patterns (written and read with agent-scope accesses)
+    float* factor;              // [L]
+    double* scal;               // [0] T, [1] KL
+    unsigned* ticket;
+    int B, L, kind; double param;
+};
+static __device__ double kl_block_sum(double v, double* red) {
+    const int tid = threadIdx.x;
+    red[tid] = v;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) red[tid] += red[tid + o];
+        __syncthreads();
+    }
+    const double r = red[0];
+    __syncthreads();
+    return r;
+}
+template <int VEC>
+static __global__ __launch_bounds__(256) void kl_shape_kernel(KlShapeArgs a) {
+    __shared__ double red[256];
+    __shared__ int is_last;
+    const int tid = threadIdx.x, d0 = blockIdx.x * VEC;
+    double s[VEC];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) s[v] = 0.0;
+    for (int b = tid; b < a.B; b += 256) {
+        float m[VEC], l[VEC];
+        const size_t at = (size_t)b * a.L + d0;
+        if constexpr (VEC == 4) {
+            const f32x4 mv = *reinterpret_cast<const f32x4*>(a.mu + at), lw = *reinterpret_cast<const f32x4*>(a.lv + at);
+#pragma unroll
+            for (int v = 0; v < 4; ++v) { m[v] = mv[v]; l[v] = lw[v]; }
+        } else { m[0] = a.mu[at]; l[0] = a.lv[at]; }
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+            const double md = m[v], ld = l[v];
+            s[v] += -0.5 * (1.0 + ld - md * md - exp(ld));
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) s[v] = kl_block_sum(s[v], red) / (double)a.B;
+    if (tid == 0) {
+#pragma unroll
+        for (int v = 0; v < VEC; ++v)
+            __hip_atomic_store(a.kl_d + d0 + v, (unsigned long long)__double_as_longlong(s[v]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned t = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int last = t == gridDim.x - 1;
+        if (last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        is_last = last;
+    }
+    __syncthreads();
+    if (!is_last) return;
+    double kl = 0.0, fb = 0.0;
+    for (int d = tid; d < a.L; d += 256) {
+        const double k = __longlong_as_double((long long)__hip_atomic_load(a.kl_d + d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        kl += k;
+        fb += k > a.param ? k : a.param;
+    }
+    kl = kl_block_sum(kl, red);
+    if (a.kind == VAE_KL_FREE_BITS) fb = kl_block_sum(fb, red);
+    const double diff = kl - a.param;
+    const float sgn = diff > 0.0 ? 1.f : (diff < 0.0 ? -1.f : 0.f);
+    for (int d = tid; d < a.L; d += 256) {
+        float f = 1.f;
+        if (a.kind == VAE_KL_FREE_BITS)
+            f = __longlong_as_double((long long)__hip_atomic_load(a.kl_d + d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) > a.param ? 1.f : 0.f;
+        else if (a.kind == VAE_KL_CAPACITY) f = sgn;
+        a.factor[d] = f;
+    }
+    if (tid == 0) {
+        a.scal[0] = a.kind == VAE_KL_FREE_BITS ? fb : (a.kind == VAE_KL_CAPACITY ? fabs(diff) : kl);
+        a.scal[1] = kl;
+    }
 }
 
 // f' (NHWC flatten: pix*256 + c) -> reference flatten index c*s2 + pix (models.py:133)

@@ -92,6 +92,7 @@ extern "C" void vae_destroy(vae_ctx* c) {
         (void)hipStreamSynchronize(c->comm);
         for (int i = 0; i < vae_ctx::NFORK; ++i) (void)hipEventDestroy(c->ev_fork[i]);
         (void)hipEventDestroy(c->ev_pack); (void)hipEventDestroy(c->ev_comm);
+        if (c->ev_kl) (void)hipEventDestroy(c->ev_kl);
         for (int i = 0; i < vae_ctx::NBUCKET; ++i) (void)hipEventDestroy(c->ev_bucket[i]);
     }
     delete c;
@@ -370,6 +371,7 @@ extern "C" int vae_forward(vae_ctx* c, const float* x, int B, const float* param
     hipStream_t st = (hipStream_t)stream;
     c->cur_stream = st; c->cur_stream_set = true;
     c->fwd_recon = c->recon;
+    c->fwd_kl_kind = c->kl_kind; c->fwd_kl_param = c->kl_param; c->kl_pending = 0;
     return VAE_DISPATCH(c->dtype, forward_impl, (c, x, B, params, bn_running, nbt, eps, seed, train, xhat, mu, lv, z, st));
 }
 
@@ -382,6 +384,7 @@ extern "C" int vae_decode(vae_ctx* c, const float* z, int B, const float* params
     c->cur_stream = st; c->cur_stream_set = true;
     // what vae_backward_ex needs of a decode-only pass (its BatchNorm mode, z, xhat, the gradient scale); vae_backward refuses it
     c->B = B; c->trained = train; c->fwd_kind = 2; c->fwd_recon = c->recon;   // (c->B: the batch statistics' count)
+    c->fwd_kl_kind = VAE_KL_PLAIN; c->kl_pending = 0;
     c->x = xhat; c->xhat = xhat; c->z = const_cast<float*>(z); c->mu = c->lv = nullptr;
     set_grad_scale(c, B);
     HIP_CHECK_RET(hipMemsetAsync(c->dstats, 0, c->n_dstats * sizeof(double), st)); c->bwd_dirty = 0;
@@ -401,7 +404,7 @@ extern "C" int vae_encode(vae_ctx* c, const float* x, int B, const float* params
     hipStream_t st = (hipStream_t)stream;
     c->cur_stream = st; c->cur_stream_set = true;
     c->fwd_recon = c->recon; c->xhat = nullptr; c->dlogit_valid = 0; c->convout_pending = 0;
-    c->fwd_kind = 1;
+    c->fwd_kind = 1; c->fwd_kl_kind = VAE_KL_PLAIN; c->kl_pending = 0;   // (no ELBO follows an encoder-only pass)
     const int rc = VAE_DISPATCH(c->dtype, encode_impl, (c, x, B, params, bn_running, nbt, eps, seed, train, mu, lv, z, st));
     if (rc) c->B = 0;
     return rc;
@@ -438,7 +441,7 @@ extern "C" int vae_log_likelihood(vae_ctx* c, const float* x, int B, const float
     // whatever happens below, the context is left without a forward to differentiate or score
     struct Reset { vae_ctx* c; ~Reset() { c->ps_part = nullptr; c->B = 0; c->trained = 0; c->dlogit_valid = 0; c->convout_pending = 0; } } reset{c};
     c->cur_stream = st; c->cur_stream_set = true;
-    c->fwd_recon = c->recon;
+    c->fwd_recon = c->recon; c->fwd_kl_kind = VAE_KL_PLAIN; c->kl_pending = 0;
     float* bnr = const_cast<float*>(bn_running);   // eval mode: read only
     int rc = VAE_DISPATCH(c->dtype, encode_impl, (c, x, B, params, bnr, nullptr, nullptr, seed, 0, mu, lv, z0, st));
     if (rc) return rc;
@@ -475,11 +478,66 @@ extern "C" int vae_set_recon_loss(vae_ctx* c, int kind) {
     return 0;
 }
 
+// ---- KL objectives (free bits, capacity target; edge_kernels.cuh: kl_shape_kernel) ---------------------------------------------
+static int check_kl_objective(const char* what, int kind, double param) {
+    if (kind != VAE_KL_PLAIN && kind != VAE_KL_FREE_BITS && kind != VAE_KL_CAPACITY) return vae_set_error(what, "kind must be VAE_KL_PLAIN, VAE_KL_FREE_BITS or VAE_KL_CAPACITY");
+    if (param != param || param < 0.0 || std::isinf(param)) return vae_set_error(what, "the parameter must be finite and >= 0");
+    if (kind == VAE_KL_FREE_BITS && !(param > 0.0)) return vae_set_error(what, "free bits need lambda > 0 nats per dimension");
+    return 0;
+}
+extern "C" int vae_set_kl_objective(vae_ctx* c, int kind, double param) {
+    if (!c) return vae_set_error("vae_set_kl_objective", "null ctx");
+    if (check_kl_objective("vae_set_kl_objective", kind, param)) return -1;
+    c->kl_kind = kind; c->kl_param = kind == VAE_KL_PLAIN ? 0.0 : param;
+    return 0;
+}
+// one launch: every size takes it (VEC = 4 where the rows allow 16-byte loads); the ticket word is zeroed in front of it
+static int enqueue_kl_shape(const float* mu, const float* lv, int B, int L, int kind, double param, unsigned long long* kl_d,
+                            double* scal, float* factor, unsigned* ticket, hipStream_t st) {
+    HIP_CHECK_RET(hipMemsetAsync(ticket, 0, 16, st));
+    KlShapeArgs a; a.mu = mu; a.lv = lv; a.kl_d = kl_d; a.factor = factor; a.scal = scal; a.ticket = ticket; a.B = B; a.L = L; a.kind = kind; a.param = param;
+    const bool vec = L % 4 == 0 && !(((uintptr_t)mu | (uintptr_t)lv) & 15);
+    if (vec) hipLaunchKernelGGL(kl_shape_kernel<4>, dim3(L / 4), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(kl_shape_kernel<1>, dim3(L), dim3(256), 0, st, a);
+    LAUNCH_CHECK("kl_shape_kernel");
+    return 0;
+}
+int launch_kl_shape(vae_ctx* c, hipStream_t st) {
+    if (!c->kl_ws) {
+        c->kl_ws = dalloc<char>(c, (size_t)c->L * 12 + 16); c->kl_tk = dalloc<unsigned>(c, 4);
+        if (!c->kl_ws || !c->kl_tk || hipEventCreateWithFlags(&c->ev_kl, hipEventDisableTiming) != hipSuccess) { c->kl_ws = nullptr; return vae_set_error("kl_shape", "allocation failed"); }
+    }
+    // always the same side stream: successive reductions of a context write the same buffers and must not overlap
+    SideFork f = fork_side(c, st, vae_ctx::KL_SIDE);
+    if (f.rc) return f.rc;
+    {
+        ProfScope ps(c, "kl_shape", 8.0 * c->B * c->L + 12.0 * c->L, 0, f.st);
+        if (enqueue_kl_shape(c->mu, c->lv, c->B, c->L, c->fwd_kl_kind, c->fwd_kl_param, c->kl_d(), c->kl_scal(), c->kl_factor(), c->kl_tk, f.st)) return -1;
+    }
+    HIP_CHECK_RET(hipEventRecord(c->ev_kl, f.st));
+    c->kl_pending = 1;
+    return 0;
+}
+int join_kl(vae_ctx* c, hipStream_t st) {
+    if (c->kl_pending) HIP_CHECK_RET(hipStreamWaitEvent(st, c->ev_kl, 0));
+    return 0;
+}
+extern "C" int vae_kl_per_dim(vae_ctx* c, double* out, vae_stream_t stream) {
+    if (!c || !c->B || !c->mu || !c->lv) return vae_set_error("vae_kl_per_dim", "no forward with a posterior (vae_forward, a training step or vae_encode)");
+    if (!out) return vae_set_error("vae_kl_per_dim", "null output pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (!c->kl_pending && launch_kl_shape(c, st)) return -1;   // (the forward was plain: reduce now)
+    if (join_kl(c, st)) return -1;
+    HIP_CHECK_RET(hipMemcpyAsync(out, c->kl_d(), (size_t)c->L * 8, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
 extern "C" int vae_loss(vae_ctx* c, float kld_weight, float* out3, vae_stream_t stream) {
     if (!c || !c->B) return vae_set_error("vae_loss", "no forward");
     if (c->convout_pending) return vae_set_error("vae_loss", "the forward ran with train = 2: the ELBO is produced by the backward (use vae_loss_deferred)");
+    if (join_kl(c, (hipStream_t)stream)) return -1;
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, c->accum, out3,
-                       1.0 / ((double)c->B * c->H * c->H), 1.0 / (double)c->B, kld_weight, STAT_R);
+                       1.0 / ((double)c->B * c->H * c->H), 1.0 / (double)c->B, kld_weight, STAT_R, c->kl_shaped());
     LAUNCH_CHECK("loss_finalize_kernel");
     return 0;
 }
@@ -493,8 +551,9 @@ extern "C" int vae_loss_deferred(vae_ctx* c, float kld_weight, float* out3, vae_
     if (c->convout_pending) { c->loss_out3 = out3; c->loss_kw = kld_weight; return 0; }   // finalised by the backward, after the fused output-conv kernel
     SideFork f = (c->knob_lean & 4) ? fork_side(c, (hipStream_t)stream) : SideFork{(hipStream_t)stream, c->slab, 0};
     if (f.rc) return f.rc;
+    if (c->kl_shaped() && join_kl(c, f.st)) return -1;
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, f.st, c->accum, out3,
-                       1.0 / ((double)c->B * c->H * c->H), 1.0 / (double)c->B, kld_weight, STAT_R);
+                       1.0 / ((double)c->B * c->H * c->H), 1.0 / (double)c->B, kld_weight, STAT_R, c->kl_shaped());
     LAUNCH_CHECK("loss_finalize_kernel");
     return 0;
 }
@@ -504,9 +563,12 @@ extern "C" int vae_loss_deferred(vae_ctx* c, float kld_weight, float* out3, vae_
 static constexpr int kGenericSlots = 64, kMaxDevices = 64;
 static double* g_generic_ring[kMaxDevices] = {nullptr};
 static unsigned g_generic_next[kMaxDevices] = {0};
-extern "C" int vae_elbo_generic_ex(const float* xhat, const float* target, const float* mu, const float* lv, int64_t n, int B, int L,
-                                   float kld_weight, int recon, float* out3, float* g_xhat, float* g_mu, float* g_lv, vae_stream_t stream) {
-    if (recon != VAE_RECON_BCE && recon != VAE_RECON_MSE) return vae_set_error("vae_elbo_generic_ex", "recon must be VAE_RECON_BCE or VAE_RECON_MSE");
+static int elbo_generic(const char* what, const float* xhat, const float* target, const float* mu, const float* lv, int64_t n, int B, int L,
+                        float kld_weight, int recon, int kl_kind, double kl_param, float* out3, float* g_xhat, float* g_mu, float* g_lv,
+                        vae_stream_t stream) {
+    if (recon != VAE_RECON_BCE && recon != VAE_RECON_MSE) return vae_set_error(what, "recon must be VAE_RECON_BCE or VAE_RECON_MSE");
+    if (check_kl_objective(what, kl_kind, kl_param)) return -1;
+    if (kl_kind != VAE_KL_PLAIN && (B < 1 || L < 1 || !mu || !lv)) return vae_set_error(what, "the KL objective needs mu / log_var [batch, latent_dim]");
     hipStream_t st = (hipStream_t)stream;
     int dev = 0;
     HIP_CHECK_RET(hipGetDevice(&dev));
@@ -522,11 +584,43 @@ extern "C" int vae_elbo_generic_ex(const float* xhat, const float* target, const
         hipLaunchKernelGGL(bce_kernel, grid, dim3(256), 0, st, xhat, target, g_xhat, acc, (long)n, (float)(1.0 / (double)n));
         LAUNCH_CHECK("bce_kernel");
     }
-    hipLaunchKernelGGL(kld_only_kernel, dim3((B * L + 255) / 256), dim3(256), 0, st, mu, lv, acc, B * L, kld_weight / (float)B, g_mu, g_lv);
-    LAUNCH_CHECK("kld_only_kernel");
-    hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, st, acc, out3, 1.0 / (double)n, 1.0 / (double)B, kld_weight, 1);
-    LAUNCH_CHECK("loss_finalize_kernel");
+    if (kl_kind == VAE_KL_PLAIN) {
+        hipLaunchKernelGGL(kld_only_kernel, dim3((B * L + 255) / 256), dim3(256), 0, st, mu, lv, acc, B * L, kld_weight / (float)B, g_mu, g_lv);
+        LAUNCH_CHECK("kld_only_kernel");
+        hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, st, acc, out3, 1.0 / (double)n, 1.0 / (double)B, kld_weight, 1);
+        LAUNCH_CHECK("loss_finalize_kernel");
+        return 0;
+    }
+    // shaped objective: the reduction in front (its work space from the stream-ordered allocator: kl_d | scalars | factor | ticket block)
+    void* ws = nullptr;
+    const size_t fac_off = (size_t)L * 8 + 16, tk_off = (fac_off + (size_t)L * 4 + 15) / 16 * 16;
+    HIP_CHECK_RET(hipMallocAsync(&ws, tk_off + 16, st));
+    char* base = static_cast<char*>(ws);
+    auto run = [&]() -> int {
+        const float* factor = reinterpret_cast<const float*>(base + fac_off);
+        const double* scal = reinterpret_cast<const double*>(base + (size_t)L * 8);
+        if (enqueue_kl_shape(mu, lv, B, L, kl_kind, kl_param, reinterpret_cast<unsigned long long*>(base), const_cast<double*>(scal),
+                             const_cast<float*>(factor), reinterpret_cast<unsigned*>(base + tk_off), st)) return -1;
+        hipLaunchKernelGGL(kld_only_kernel, dim3((B * L + 255) / 256), dim3(256), 0, st, mu, lv, acc, B * L, kld_weight / (float)B, g_mu, g_lv, factor, L);
+        LAUNCH_CHECK("kld_only_kernel");
+        hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, st, acc, out3, 1.0 / (double)n, 1.0 / (double)B, kld_weight, 1, scal);
+        LAUNCH_CHECK("loss_finalize_kernel");
+        return 0;
+    };
+    const int rc = run();
+    const hipError_t fe = hipFreeAsync(ws, st);
+    if (rc) return rc;
+    if (fe != hipSuccess) return vae_set_error("hipFreeAsync", hipGetErrorString(fe));
     return 0;
+}
+extern "C" int vae_elbo_generic_ex(const float* xhat, const float* target, const float* mu, const float* lv, int64_t n, int B, int L,
+                                   float kld_weight, int recon, float* out3, float* g_xhat, float* g_mu, float* g_lv, vae_stream_t stream) {
+    return elbo_generic("vae_elbo_generic_ex", xhat, target, mu, lv, n, B, L, kld_weight, recon, VAE_KL_PLAIN, 0.0, out3, g_xhat, g_mu, g_lv, stream);
+}
+extern "C" int vae_elbo_generic_kl(const float* xhat, const float* target, const float* mu, const float* lv, int64_t n, int B, int L,
+                                   float kld_weight, int recon, int kl_kind, double kl_param, float* out3, float* g_xhat, float* g_mu,
+                                   float* g_lv, vae_stream_t stream) {
+    return elbo_generic("vae_elbo_generic_kl", xhat, target, mu, lv, n, B, L, kld_weight, recon, kl_kind, kl_param, out3, g_xhat, g_mu, g_lv, stream);
 }
 extern "C" int vae_elbo_generic(const float* xhat, const float* target, const float* mu, const float* lv, int64_t n, int B, int L,
                                 float kld_weight, float* out3, float* g_xhat, float* g_mu, float* g_lv, vae_stream_t stream) {
@@ -912,6 +1006,19 @@ extern "C" int vae_last_eps(vae_ctx* c, float* out, vae_stream_t stream) {
 extern "C" int vae_debug_tensor(vae_ctx* c, int which, float* out, int64_t capacity, vae_stream_t stream) {
     if (!c || !c->B) return vae_set_error("vae_debug_tensor", "no forward");
     const void* src; int C, HW;
+    if (which == 18) {   // the latent gradient [B, 2L] f32: no layout to convert
+        const long n = (long)c->B * 2 * c->L;
+        if (n > capacity) return vae_set_error("vae_debug_tensor", "output too small");
+        HIP_CHECK_RET(hipMemcpyAsync(out, c->dlat, (size_t)n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        return 0;
+    }
+    if (which == 19) {   // the per-dimension factors of the last forward's KL objective [L] f32 (an objective other than plain)
+        if (c->fwd_kl_kind == VAE_KL_PLAIN || !c->kl_pending) return vae_set_error("vae_debug_tensor", "the last forward ran with the plain KL objective");
+        if (c->L > capacity) return vae_set_error("vae_debug_tensor", "output too small");
+        if (join_kl(c, (hipStream_t)stream)) return -1;
+        HIP_CHECK_RET(hipMemcpyAsync(out, c->kl_factor(), (size_t)c->L * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        return 0;
+    }
     if (which >= 0 && which < 16) { const BnLayer& l = c->lay[which & 7]; src = which < 8 ? l.y : l.dz; C = l.C; HW = l.H * l.W; }
     else if (which == 16 || which == 17) { src = which == 16 ? c->d0 : c->dd0; C = 256; HW = c->s2; }
     else return vae_set_error("vae_debug_tensor", "bad tensor id");

@@ -119,6 +119,16 @@ struct vae_ctx {
     // reconstruction term of the ELBO (VAE_RECON_*): recon is the setting for the following forwards (vae_set_recon_loss);
     // fwd_recon is what the last forward was run with - its deferred output conv, loss and backward use that one
     int recon = VAE_RECON_BCE, fwd_recon = VAE_RECON_BCE;
+    // KL objective (VAE_KL_*): kl_kind / kl_param are the setting for the following forwards (vae_set_kl_objective), fwd_kl_* what
+    // the last forward recorded.  kl_ws (allocated on first use): kl_d [L] f64 | scalars {T, KL} f64 | factor [L] f32 (kl_tk: the ticket word, a 16-byte block of its own), written by
+    // kl_shape_kernel on side stream KL_SIDE; ev_kl follows it and kl_pending says that consumers of this forward must wait for it.
+    int kl_kind = VAE_KL_PLAIN, fwd_kl_kind = VAE_KL_PLAIN; double kl_param = 0.0, fwd_kl_param = 0.0;
+    static constexpr int KL_SIDE = 2;
+    void* kl_ws = nullptr; unsigned* kl_tk = nullptr; hipEvent_t ev_kl = nullptr; int kl_pending = 0;
+    unsigned long long* kl_d() const { return static_cast<unsigned long long*>(kl_ws); }
+    double* kl_scal() const { return reinterpret_cast<double*>(kl_d() + L); }
+    float* kl_factor() const { return reinterpret_cast<float*>(kl_scal() + 2); }
+    const double* kl_shaped() const { return fwd_kl_kind != VAE_KL_PLAIN ? kl_scal() : nullptr; }   // loss_finalize_kernel's argument
     // vae_log_likelihood: ps_part (non-null only during its decoder passes) switches the output conv to its per-sample mode
     // (tile partials, target x[b mod ps_tb]; ps_ntile: tiles per image of the kernel taken).  ll_*: its scratch, allocated on first use.
     double* ps_part = nullptr; int ps_tb = 0, ps_ntile = 0;
@@ -188,6 +198,10 @@ struct SideFork { hipStream_t st; float* slab; int rc; };
 SideFork fork_side(vae_ctx* c, hipStream_t st, int which = -1);
 int join_sides(vae_ctx* c, hipStream_t st);
 int join_comm(vae_ctx* c, hipStream_t st);
+// KL objectives (vae_api.hip): the reduction of the last forward's mu / log_var on side stream KL_SIDE, forked from `st`; and the
+// wait a consumer's stream needs before it reads the factors / scalars (nothing when no reduction is outstanding)
+int launch_kl_shape(vae_ctx* c, hipStream_t st);
+int join_kl(vae_ctx* c, hipStream_t st);
 
 // entry points instantiated once per storage type (impl_bf16.hip, impl_f16.hip, impl_f32.hip)
 template <typename T> int pack_weights(vae_ctx* c, const float* params, hipStream_t st);

@@ -646,6 +646,8 @@ int forward_impl(vae_ctx* c, const float* x, int B, const float* params, float* 
     c->xhat = xhat; c->fwd_kind = 0;
     const int rc = encode_impl<T>(c, x, B, params, bn_running, nbt, eps, seed, train, mu, lv, z, st);
     if (rc) return rc;
+    // free bits / capacity target: the batch reduction its loss and backward need, beside the decoder (nothing for the plain objective)
+    if (c->fwd_kl_kind != VAE_KL_PLAIN && launch_kl_shape(c, st)) return -1;
     return decode_impl<T>(c, z, B, params, bn_running, nbt, train, x, xhat, st);
 }
 
@@ -872,8 +874,9 @@ static int backward_first(vae_ctx* c, const float* x, const float* params, float
         hipLaunchKernelGGL(accum_to_f32_kernel, dim3(1), dim3(64), 0, f.st, c->accum + 2, grads + c->poff[39], c->ginv);
         LAUNCH_CHECK("accum_to_f32_kernel");
         if (step7 && c->loss_out3) {   // the ELBO scalars vae_loss_deferred asked for: the BCE sum exists only now
+            if (c->kl_shaped() && join_kl(c, f.st)) return -1;
             hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, f.st, c->accum, c->loss_out3,
-                               1.0 / ((double)B * H * H), 1.0 / (double)B, c->loss_kw, STAT_R);
+                               1.0 / ((double)B * H * H), 1.0 / (double)B, c->loss_kw, STAT_R, c->kl_shaped());
             LAUNCH_CHECK("loss_finalize_kernel");
             c->loss_out3 = nullptr;
         }
@@ -983,7 +986,12 @@ static int backward_second(vae_ctx* c, const float* x, const float* params, floa
         LatentBwdArgs lb;
         lb.slab = c->slab; lb.nslab = nsplit; lb.npad = c->npad_di; lb.mu = c->mu; lb.lv = c->lv; lb.eps = c->eps; lb.gscale = gscale;
         lb.gmu = g_mu; lb.glv = g_lv; lb.gz = g_z; lb.dlat = c->dlat; lb.B = B; lb.L = L; lb.kld_weight = kld_weight; lb.add_kl = add_kl; lb.gmul = c->gmul;
-        hipLaunchKernelGGL(latent_bwd_kernel, dim3((B * L * LAT_LANES + 255) / 256), dim3(256), 0, st, lb);
+        lb.factor = nullptr;
+        if (add_kl && c->fwd_kl_kind != VAE_KL_PLAIN) {   // the objective the forward recorded: its per-dimension factors
+            if (join_kl(c, st)) return -1;
+            lb.factor = c->kl_factor();
+            hipLaunchKernelGGL(latent_bwd_kernel<true>, dim3((B * L * LAT_LANES + 255) / 256), dim3(256), 0, st, lb);
+        } else hipLaunchKernelGGL(latent_bwd_kernel<false>, dim3((B * L * LAT_LANES + 255) / 256), dim3(256), 0, st, lb);
         LAUNCH_CHECK("latent_bwd_kernel");
         if (!lat_mfma) {
             SideFork f = fork_side(c, st);

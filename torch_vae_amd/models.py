@@ -26,6 +26,16 @@ Deviations from the reference, all explicit:
     ``F.mse_loss(xhat, x)`` - a Gaussian likelihood for velocity-valued rolls
     with targets anywhere in [0, 1].  ``model.recon_loss`` may be reassigned; it
     is read at every forward and fused step.  ``loss()`` keys are unchanged.
+  * ``kl_free_bits`` / ``kl_capacity`` (keyword-only; default off, the
+    reference's plain KL) replace the KL term of the ELBO by
+    ``sum_d max(kl_d, kl_free_bits)`` (Kingma et al. 2016; ``kl_d`` the batch
+    mean of dimension d's KL, nats) or ``|KL - kl_capacity|`` (Burgess et al.
+    2018; ``kld_weight`` plays gamma).  Both are attributes read at every forward
+    and fused step; ``kld_loss`` stays the raw KL.  The reduction and the mask
+    / sign decision run on the device in f64, in a fixed order.  Data parallel:
+    ``kl_d`` and ``KL`` are the replica's OWN batch means (as BatchNorm
+    statistics are per replica), so replicas may mask different dimensions in
+    a step; the all-reduce averages the resulting gradients.
 """
 from __future__ import annotations
 
@@ -54,6 +64,21 @@ def _recon_kind(name) -> int:
     return kind
 
 
+def _kl_objective(free_bits, capacity) -> tuple[int, float]:
+    """(VAE_KL_* kind, parameter) of the kl_free_bits / kl_capacity pair; ValueError on anything the library would refuse."""
+    def number(v, name):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+            raise ValueError(f"{name} must be a finite number >= 0, got {v!r}")
+        return float(v)
+    fb = number(free_bits, "kl_free_bits")
+    if capacity is None:
+        return (_lib.KL_FREE_BITS, fb) if fb > 0.0 else (_lib.KL_PLAIN, 0.0)
+    cap = number(capacity, "kl_capacity")
+    if fb > 0.0:
+        raise ValueError("kl_free_bits and kl_capacity are alternatives: set one of them")
+    return _lib.KL_CAPACITY, cap
+
+
 _NULL_GUARD = contextlib.nullcontext()
 
 
@@ -75,11 +100,17 @@ class _Context:
         if not self.handle:
             raise _lib.VaeLibError("vae_create: " + _lib.lib().vae_last_error().decode())
         self.recon = _lib.RECON_BCE     # the library's default (vae_set_recon_loss)
+        self.kl = (_lib.KL_PLAIN, 0.0)  # the library's default (vae_set_kl_objective)
 
     def set_recon(self, kind: int):
         if kind != self.recon:
             _lib.check(_lib.lib().vae_set_recon_loss(self.handle, kind), "vae_set_recon_loss")
             self.recon = kind
+
+    def set_kl(self, kl: tuple[int, float]):
+        if kl != self.kl:               # (never for a model that leaves both options off: no call beyond the library's default)
+            _lib.check(_lib.lib().vae_set_kl_objective(self.handle, kl[0], kl[1]), "vae_set_kl_objective")
+            self.kl = kl
 
     def __del__(self):
         try:
@@ -180,15 +211,21 @@ class _GenericELBO(torch.autograd.Function):
     """VanillaVAE.loss on tensors that are not the model's own last forward."""
 
     @staticmethod
-    def forward(ctx, xhat, target, mu, lv, kld_weight, recon):
+    def forward(ctx, xhat, target, mu, lv, kld_weight, recon, kl=(_lib.KL_PLAIN, 0.0)):
         xhat, target, mu, lv = (t.contiguous().float() for t in (xhat, target, mu, lv))
         out3 = torch.empty(3, device=xhat.device, dtype=torch.float32)
         gx, gm, gl = torch.empty_like(xhat), torch.empty_like(mu), torch.empty_like(lv)
         with torch.cuda.device(xhat.device):
-            _lib.check(_lib.lib().vae_elbo_generic_ex(xhat.data_ptr(), target.data_ptr(), mu.data_ptr(), lv.data_ptr(),
-                                                     xhat.numel(), mu.shape[0], mu.shape[1], float(kld_weight), int(recon),
-                                                     out3.data_ptr(), gx.data_ptr(), gm.data_ptr(), gl.data_ptr(),
-                                                     _stream_ptr(xhat.device)), "vae_elbo_generic_ex")
+            if kl[0] != _lib.KL_PLAIN:
+                _lib.check(_lib.lib().vae_elbo_generic_kl(xhat.data_ptr(), target.data_ptr(), mu.data_ptr(), lv.data_ptr(),
+                                                         xhat.numel(), mu.shape[0], mu.shape[1], float(kld_weight), int(recon),
+                                                         int(kl[0]), float(kl[1]), out3.data_ptr(), gx.data_ptr(), gm.data_ptr(),
+                                                         gl.data_ptr(), _stream_ptr(xhat.device)), "vae_elbo_generic_kl")
+            else:
+                _lib.check(_lib.lib().vae_elbo_generic_ex(xhat.data_ptr(), target.data_ptr(), mu.data_ptr(), lv.data_ptr(),
+                                                         xhat.numel(), mu.shape[0], mu.shape[1], float(kld_weight), int(recon),
+                                                         out3.data_ptr(), gx.data_ptr(), gm.data_ptr(), gl.data_ptr(),
+                                                         _stream_ptr(xhat.device)), "vae_elbo_generic_ex")
         ctx.save_for_backward(gx, gm, gl)
         ctx.mark_non_differentiable(out3)
         return out3[0].clone(), out3
@@ -196,7 +233,7 @@ class _GenericELBO(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, _g_out3):
         gx, gm, gl = ctx.saved_tensors
-        return gx * g_loss, None, gm * g_loss, gl * g_loss, None, None
+        return gx * g_loss, None, gm * g_loss, gl * g_loss, None, None, None
 
 
 class VanillaVAE(nn.Module):
@@ -215,6 +252,8 @@ class VanillaVAE(nn.Module):
         compute_dtype: str = "bf16",
         recon_loss: str = "bce",
         max_batch: int | None = None,
+        kl_free_bits: float = 0.0,
+        kl_capacity: float | None = None,
     ):
         super().__init__()
         if in_channels != 1:
@@ -238,6 +277,9 @@ class VanillaVAE(nn.Module):
         self.compute_dtype = compute_dtype
         _recon_kind(recon_loss)
         self.recon_loss = recon_loss
+        _kl_objective(kl_free_bits, kl_capacity)
+        self.kl_free_bits = kl_free_bits
+        self.kl_capacity = kl_capacity
         s = self.img_size // 16 if self.generalised else 2
         self.last_conv_size = s * s  # models.py:33 hard-wires 4
         self.flattened_size = self.last_conv_size * hidden_dims[-1]
@@ -408,6 +450,8 @@ class VanillaVAE(nn.Module):
                     self._init_library_comm()
             self._max_batch = need
         self._ctx.set_recon(_recon_kind(self.recon_loss))
+        if self.kl_capacity is not None or self.kl_free_bits != 0.0 or self._ctx.kl[0] != _lib.KL_PLAIN:
+            self._ctx.set_kl(_kl_objective(self.kl_free_bits, self.kl_capacity))
         return self._ctx
 
     # -- data parallel: the step library's own RCCL communicator (include/vae_step.h: vae_comm_*) ----------------------
@@ -762,8 +806,22 @@ class VanillaVAE(nn.Module):
             loss = out3[0].clone()
         else:
             loss, out3 = _GenericELBO.apply(output["output"], output["input"], output["encoded"]["mu"],
-                                            output["encoded"]["log_var"], self.kld_weight, _recon_kind(self.recon_loss))
+                                            output["encoded"]["log_var"], self.kld_weight, _recon_kind(self.recon_loss),
+                                            _kl_objective(self.kl_free_bits, self.kl_capacity))
         return LossOutput(loss=loss, reconstruction_loss=out3[1].detach(), kld_loss=out3[2].detach())
+
+    def kl_per_dim(self) -> Tensor:
+        """Batch-mean KL of every latent dimension (nats) for the model's last forward / fused step / encode: a float64
+        [latent_dim] device tensor, reduced in a fixed order, with no host synchronisation - a per-step collapse monitor that can
+        stay on the device.  With kl_free_bits / kl_capacity set it is the very reduction the step's mask was decided on.  Data
+        parallel: the replica's own batch."""
+        self._require_device()
+        if self._last is None or self._last.get("kind", "forward") == "decode" or self._ctx is None:
+            raise RuntimeError("kl_per_dim needs a forward, fused step or encode of this model")
+        out = torch.empty(self.latent_dim, device=self._flat.device, dtype=torch.float64)
+        with self._device_guard():
+            _lib.check(_lib.lib().vae_kl_per_dim(self._ctx.handle, out.data_ptr(), self._stream()), "vae_kl_per_dim")
+        return out
 
     def sample(self, num_samples: int, current_device: int, **kwargs) -> Tensor:
         """models.py:250-263: z ~ N(0, I) on the host generator, moved to the device, decoded."""

@@ -8,6 +8,7 @@ model is this package's VanillaVAE, the criterion is ``model.loss`` and the opti
 still runs through the same kernels via autograd.  With ``torch.distributed`` initialised
 (one process per GPU, RCCL) the optimised gradient ranges are all-reduced before the update
 -- plain data parallelism, which the reference only prepares for (train.py:165-166,201,663).
+``KLSchedule`` moves ``model.kld_weight`` (and a KL capacity target) per step when the config asks for it.
 """
 from __future__ import annotations
 
@@ -176,6 +177,61 @@ def fused_step(model: VanillaVAE, optimizer, x, eps=None, use_device_eps: bool =
     return out3, xhat
 
 
+class KLSchedule:
+    """KL weight (and, optionally, KL capacity) as a pure function of the 0-based global step ``t`` - ``total_step`` before the
+    step is taken - so a run resumed from a checkpoint's ``total_step`` continues the schedule with no state of its own.
+      "constant": beta
+      "linear":   beta * min(1, t / warmup_steps)                                         (KL warm-up, Bowman et al. 2016)
+      "cyclical": tau = (t mod period) / period,  beta * min(1, tau / ratio), ratio in (0, 1]  (Fu et al. 2019)
+    capacity ramp (Burgess et al. 2018): C(t) = capacity_max * min(1, t / capacity_steps); None when capacity_max is None.
+    The reference names the idea ("option: increase kld_weight over time", models.py:218-219) and logs the weight every step."""
+
+    KINDS = ("constant", "linear", "cyclical")
+
+    def __init__(self, kind: str = "constant", beta: float = 1.0, warmup_steps: int = 0, period: int = 0, ratio: float = 0.5,
+                 capacity_max: float | None = None, capacity_steps: int = 0):
+        if kind not in self.KINDS:
+            raise ValueError(f"kl_schedule must be one of {self.KINDS}, got {kind!r}")
+        if not (beta >= 0.0) or beta == float("inf"):
+            raise ValueError(f"kl_beta must be finite and >= 0, got {beta!r}")
+        if kind == "linear" and int(warmup_steps) < 1:
+            raise ValueError("a linear KL schedule needs kl_warmup_steps >= 1")
+        if kind == "cyclical" and (int(period) < 1 or not (0.0 < ratio <= 1.0)):
+            raise ValueError("a cyclical KL schedule needs kl_cycle_steps >= 1 and 0 < kl_cycle_ratio <= 1")
+        if capacity_max is not None and (not (capacity_max >= 0.0) or capacity_max == float("inf") or int(capacity_steps) < 1):
+            raise ValueError("a capacity ramp needs a finite kl_capacity_max >= 0 and kl_capacity_steps >= 1")
+        self.kind, self.beta, self.warmup_steps, self.period, self.ratio = kind, float(beta), int(warmup_steps), int(period), float(ratio)
+        self.capacity_max = None if capacity_max is None else float(capacity_max)
+        self.capacity_steps = int(capacity_steps)
+
+    def value(self, t: int) -> float:
+        if self.kind == "linear":
+            return self.beta * min(1.0, t / self.warmup_steps)
+        if self.kind == "cyclical":
+            return self.beta * min(1.0, ((t % self.period) / self.period) / self.ratio)
+        return self.beta
+
+    def capacity(self, t: int) -> float | None:
+        if self.capacity_max is None:
+            return None
+        return self.capacity_max * min(1.0, t / self.capacity_steps)
+
+    @classmethod
+    def from_config(cls, config, model) -> "KLSchedule | None":
+        """The schedule ``config`` asks for (``kl_schedule``, ``kl_beta``, ``kl_warmup_steps``, ``kl_cycle_steps``,
+        ``kl_cycle_ratio``, ``kl_capacity_max``, ``kl_capacity_steps``), or None when it names neither a schedule nor a capacity
+        ramp.  The target beta is ``config.kl_beta``; when absent, the first call stores the model's ``kld_weight`` there, so
+        later epochs (which find ``model.kld_weight`` overwritten by the schedule) and a resumed run ramp towards the same value."""
+        kind = getattr(config, "kl_schedule", None)
+        cap = getattr(config, "kl_capacity_max", None)
+        if kind is None and cap is None:
+            return None
+        if getattr(config, "kl_beta", None) is None:
+            config.kl_beta = float(model.kld_weight)
+        return cls(kind or "constant", config.kl_beta, getattr(config, "kl_warmup_steps", 0), getattr(config, "kl_cycle_steps", 0),
+                   getattr(config, "kl_cycle_ratio", 0.5), cap, getattr(config, "kl_capacity_steps", 0))
+
+
 def pack_bits(stimuli: torch.Tensor) -> torch.Tensor:
     """Host-side helper for dataloaders: a 0/1 pianoroll batch [B,1,H,W] (any dtype) as bit planes [B,1,H,W/8] uint8 (most
     significant bit first, numpy.packbits order) - 1/32 of the float32 bytes.  train_one_epoch expands such batches on the device."""
@@ -241,6 +297,11 @@ def train_one_epoch(config, model, optimizer, scheduler, criterion, dataloader, 
     torch_clip = max_grad_norm is not None and not isinstance(optimizer, FusedAdamW)
     fused_clip = isinstance(optimizer, FusedAdamW) and optimizer._clip_on
     grad_norm = None
+    # KL control (optional config fields; none of them: exactly the loop without it): free bits go to the model once, the weight
+    # and the capacity are host numbers set before each step - every step entry point takes them per call, nothing synchronises
+    kl_schedule = KLSchedule.from_config(config, model)
+    if getattr(config, "kl_free_bits", None) is not None:
+        model.kl_free_bits = config.kl_free_bits
     n_batches = len(dataloader)
     in_flight = deque()   # pinned host batches a device kernel may still be reading, with the event that follows that kernel
     for batch_idx, (stimuli, y_true) in enumerate(dataloader):
@@ -261,6 +322,10 @@ def train_one_epoch(config, model, optimizer, scheduler, criterion, dataloader, 
                 in_flight.popleft()
             if len(in_flight) > 8:
                 in_flight.popleft()[1].synchronize()
+        if kl_schedule is not None:
+            model.kld_weight = kl_schedule.value(total_step)
+            if kl_schedule.capacity_max is not None:
+                model.kl_capacity = kl_schedule.capacity(total_step)
         if fused:
             # train.py:634-656 as one HIP chain: forward, ELBO, backward, [all-reduce], AdamW
             out3, reconstruction = fused_step(model, optimizer, stimuli, use_device_eps=False)
