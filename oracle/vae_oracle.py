@@ -291,6 +291,20 @@ def bn_eval_fwd(y, gamma, beta, rm, rv):
     return (y - rm.reshape(1, -1, 1, 1)) * (gamma * invstd).reshape(1, -1, 1, 1) + beta.reshape(1, -1, 1, 1)
 
 
+def bn_eval_bwd(dz, y, gamma, rm, rv):
+    """BatchNorm2d backward on the running statistics (eval mode): invstd = 1/sqrt(rv + eps) is a constant, so
+    dy = dz * gamma * invstd, dgamma = sum dz * (y - rm) * invstd, dbeta = sum dz.  Unlike train mode the bias of the conv in
+    front has a gradient: dconv_bias = sum dy = gamma * invstd * sum dz.  Returns (dy, dgamma, dbeta, dconv_bias); plain f64 -
+    the storage emulation (rounded dz, rounded dy operand) stays at the call site, as for bn_train_bwd."""
+    dz, y = np.asarray(dz, np.float64), np.asarray(y, np.float64)
+    gamma, rm, rv = (np.asarray(v, np.float64) for v in (gamma, rm, rv))
+    invstd = 1.0 / np.sqrt(rv + BN_EPS)
+    g = (gamma * invstd).reshape(1, -1, 1, 1)
+    dbeta = dz.sum(axis=(0, 2, 3))
+    dgamma = (dz * (y - rm.reshape(1, -1, 1, 1)) * invstd.reshape(1, -1, 1, 1)).sum(axis=(0, 2, 3))
+    return dz * g, dgamma, dbeta, gamma * invstd * dbeta
+
+
 def bn_eval_fwd_stored(y, gamma, beta, rm, rv, storage):
     """bn_eval_fwd the way the HIP kernels form it (torch_vae_amd/csrc/edge_kernels.cuh bn_eval_coef_kernel + the consumer's staging):
     ONE f32 fused multiply-add with f32 coefficients sc = gamma / sqrt(rv + eps), sh = beta - rm * sc derived in double.

@@ -10,6 +10,7 @@ import torch.nn.functional as F
 
 from oracle import vae_oracle as vo
 from tests.test_loglik_gpu import model_for
+from tests.path_local import LOSS_SCALE, upstream_weights
 from tests.util import PRE_BN_BIAS, rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -133,6 +134,46 @@ def test_eval_backward_and_input_gradient_match_torch(H, L, B, gen):
     after = bn_buffers(m)
     for k in before:
         assert torch.equal(before[k], after[k]), k
+
+
+@pytest.mark.parametrize("mode", ["eval", "train"])
+@pytest.mark.parametrize("H,L,B,gen", [(32, 16, 5, False), (64, 16, 3, True), (32, 300, 3, False)])
+def test_every_upstream_gradient_and_a_loss_scale_match_torch(mode, H, L, B, gen):
+    """The upstream-gradient arguments of the C ABI end to end (g_xhat, g_mu, g_lv, g_z on latents, g_pre on pre_latents in the
+    reference's NCHW-flatten order, gscale != 1): the ELBO plus a random-weighted sum on each of the five outputs, times a scale that
+    is no power of two, against torch f64 autograd of the same loss.  eval: x.requires_grad (vae_backward_ex, dx compared);
+    train: plain vae_backward.  (tests/test_grad_paths_local_gpu.py checks the same kernels layer by layer, with formulas it shares
+    with their authors; this check shares none.)"""
+    train = mode == "train"
+    m = model_for(H, L, gen, "f32", "bce", seed=160 + B)
+    m.kld_weight = 2.5
+    m.train(train)
+    x, eps = inputs(B, H, L, 161 + B)
+    P, bufs, s = ref_state(m)
+    w = {k: torch.from_numpy(v).float() for k, v in upstream_weights("forward", H, L, B, 256 * s * s, 162).items()}
+
+    def composite(out, elbo, cast):
+        enc = out["encoded"]
+        t = {"output": out["output"], "mu": enc["mu"], "log_var": enc["log_var"], "latents": out["latents"], "pre_latents": enc["pre_latents"]}
+        return LOSS_SCALE * (elbo + sum((t[k] * cast(w[k])).sum() for k in w))
+
+    xg = x.cuda().requires_grad_(not train)
+    m.set_next_eps(eps.cuda())
+    out = m(xg)
+    lo = composite(out, m.loss(out)["loss"], lambda v: v.cuda())
+    lo.backward()
+    torch.cuda.synchronize()
+    xr = x.double().requires_grad_(True)
+    mu, lv, pre = ref_encode(P, bufs, xr, train)
+    z = eps.double() * torch.exp(0.5 * lv) + mu
+    xh = ref_decode(P, bufs, z, s, train)
+    ref_out = {"output": xh, "latents": z, "encoded": {"mu": mu, "log_var": lv, "pre_latents": pre}}
+    want = composite(ref_out, ref_elbo(xh, x.double(), mu, lv, 2.5), lambda v: v.double())
+    want.backward()
+    assert abs(lo.item() - want.item()) <= LOSS_TOL * abs(want.item())
+    check_grads(grads_of(m), P, GRAD_TOL["f32"], tag=mode, train=train)
+    if not train:
+        assert rel_l2(xg.grad.cpu().numpy(), xr.grad.numpy()) < GRAD_TOL["f32"]
 
 
 @pytest.mark.parametrize("mode", ["eval", "train"])

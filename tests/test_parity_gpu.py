@@ -19,7 +19,7 @@ import pytest
 import torch
 
 from oracle import vae_oracle as vo
-from tests.util import CASES, PRE_BN_BIAS, flat_grad_dict, load_params, make_model, perturbed_params, rel_l2
+from tests.util import CASES, PRE_BN_BIAS, fetch_debug_tensor, flat_grad_dict, load_params, make_model, perturbed_params, rel_l2
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -1558,14 +1558,8 @@ def _layer_local_gaps(dtype, H, L, B, gen, seed=41, opts=None, kld_weight=1.0, e
     s = H // 16 if gen else 2
     HW = [H // 2, H // 4, H // 8, s, 2 * s, 4 * s, 8 * s, 16 * s]
     gs = vo.f16_grad_scale(B, H) if dtype == "f16" else 1.0
-    st = torch.cuda.current_stream().cuda_stream
 
-    def fetch(which, shape, scale=1.0):
-        n = int(np.prod(shape))
-        t = torch.empty(n, device="cuda")
-        _lib.check(_lib.lib().vae_debug_tensor(m._ctx.handle, which, t.data_ptr(), n, st), "dbg")
-        torch.cuda.synchronize()
-        return t.cpu().numpy().reshape(shape).astype(np.float64) / scale
+    fetch = lambda which, shape, scale=1.0: fetch_debug_tensor(m, which, shape, scale)   # noqa: E731
 
     Y = [fetch(i, (B, C[i], HW[i], HW[i])) for i in range(8)]
     DZ = [fetch(8 + i, (B, C[i], HW[i], HW[i]), gs) for i in range(8)]
@@ -1778,14 +1772,8 @@ def test_eval_mode_forward_kernels_against_oracle_on_their_own_inputs(dtype, H, 
     C = [32, 64, 128, 256, 128, 64, 32, 32]
     s = H // 16 if gen else 2
     HW = [H // 2, H // 4, H // 8, s, 2 * s, 4 * s, 8 * s, 16 * s]
-    st = torch.cuda.current_stream().cuda_stream
 
-    def fetch(which, shape):
-        n = int(np.prod(shape))
-        t = torch.empty(n, device="cuda")
-        _lib.check(_lib.lib().vae_debug_tensor(m._ctx.handle, which, t.data_ptr(), n, st), "dbg")
-        torch.cuda.synchronize()
-        return t.cpu().numpy().reshape(shape).astype(np.float64)
+    fetch = lambda which, shape: fetch_debug_tensor(m, which, shape)   # noqa: E731
 
     Y = [fetch(i, (B, C[i], HW[i], HW[i])) for i in range(8)]
     d0 = fetch(16, (B, 256, s, s))

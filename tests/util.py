@@ -64,3 +64,16 @@ def flat_grad_dict(model):
     from torch_vae_amd import _lib
     g = model.flat_grads().detach().cpu().numpy()
     return {n: g[model._offs[i]:model._offs[i] + model._sizes[i]].copy() for i, n in enumerate(_lib.PARAM_NAMES)}
+
+
+def fetch_debug_tensor(model, which, shape, scale=1.0):
+    """A tensor the model's context stored for its last forward / backward (vae_debug_tensor: 0..7 y_l, 8..15 dz_l, 16 decoder_input's
+    output, 17 its gradient, 18 the latent gradient [B, 2L]) as float64 in the reference's NCHW layout, divided by `scale` (the
+    power of two the f16 mode's stored gradients carry)."""
+    import torch
+    from torch_vae_amd import _lib
+    n = int(np.prod(shape))
+    t = torch.empty(n, device="cuda")
+    _lib.check(_lib.lib().vae_debug_tensor(model._ctx.handle, which, t.data_ptr(), n, torch.cuda.current_stream().cuda_stream), "dbg")
+    torch.cuda.synchronize()
+    return t.cpu().numpy().reshape(shape).astype(np.float64) / scale
