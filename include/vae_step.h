@@ -18,6 +18,14 @@
  * synchronise with them.  Functions return
  * 0 on success or a negative code, with the message in vae_last_error().  A context is
  * not re-entrant; use one per process / GPU.
+ *
+ * A context holds at most ONE forward (vae_forward, a training step, vae_encode or vae_decode):
+ * vae_loss*, vae_backward* and the read-back calls act on it, and the next forward replaces it.
+ * A call refused for its arguments (null pointer, batch above max_batch) touches nothing: the
+ * previous forward is still held.  A forward-type call that fails after it has started leaves
+ * the context holding NO forward - what follows is refused until the next one succeeds.
+ * Every forward also starts a new backward: vae_backward_part with part = 2 is refused unless
+ * part 1 ran on the SAME forward, and a vae_loss_deferred request dies with its forward.
  */
 #ifndef VAE_STEP_H
 #define VAE_STEP_H
@@ -339,41 +347,86 @@ int vae_debug_stamps(vae_ctx* ctx, const char* tag, int epi, long long* out);
 int vae_debug_tensor(vae_ctx* ctx, int which, float* out, int64_t capacity, vae_stream_t stream);
 /* hardware self-test of the transposed LDS read used by the bf16 weight-gradient kernel */
 int vae_selftest_tr16(vae_stream_t stream);
-/* Tuning / diagnostic switches (defaults in brackets):
- *   use_tr16 [1]            ds_read_b64_tr_b16 in the bf16 weight-gradient kernel
- *   use_mfma_convout [1]    MFMA versions of the output-conv kernels (bf16)
+/* Tuning / diagnostic switches, each listed once as `name [default]`: the default is the value that, passed to vae_set_option,
+ * restores the default behaviour (vae_option_info reports the same list).  Figures are MI355X measurements at 128x128, latent 16,
+ * batch 256, bf16, and are the record of what was tried.  "16-bit" = bf16 / f16 storage.  An unknown name returns -1.
+ * Kernel paths:
+ *   use_tr16 [1]            ds_read_b64_tr_b16 in the 16-bit weight-gradient kernels
+ *   use_mfma_convout [1]    MFMA versions of the output-conv kernels (16-bit)
  *   use_pipelined [1]       persistent prefetching conv kernels (0: one tile per workgroup)
- *   use_side_stream [1]     weight gradients / weight packing on the context's side streams
+ *   use_side_stream [1]     weight gradients / weight packing on the context's side streams (the environment variable
+ *                           VAE_NO_SIDE_STREAM makes 0 the default of a new context)
  *   use_fused_bn [1]        BatchNorm finalisation inside the consumer kernel's prologue
- *   use_fused_convout [1]   honour train = 2 (output conv forward + backward as one kernel; 16-bit storage);
- *                           knob_convout_step_grid [1024] its persistent workgroups (swept 512-4096: 1.328 / 1.323 / 1.334 / 1.341 / 1.354 ms)
- *   use_fused_wgrad [3]     bit 0: one pass over (dz, y) for the input AND weight gradient of final_layer.0 / decoder.2 / encoder.1
- *                           (16-bit storage; conv_fused.cuh): bit 0 the transposed-conv layers final_layer.0 / decoder.2, bit 1
- *                           encoder.1; knob_fused_grid [256] their persistent workgroups; use_recomp_dz [0] final_layer.0's dz
- *                           recomputed from dlogit instead of stored (bit-identical, measured slower);
- *                           use_raw_wgrad [0] deep weight gradients from operands materialised by the input-gradient kernels
- *                           (bit-identical, measured 1 % slower)
- *   knob_down_waves [8]     waves of the wide stride-2 conv kernels: 8 = 2x4 wave grid on 128-channel tiles and (knob_lay42 [1]) 4x2 on
- *                           64-channel tiles, 4 = 2x2
- *   knob_up_nt_max [1]      output channels per workgroup tile of the transposed-conv kernels in 32-channel blocks (1: more, smaller
- *                           workgroups at two waves per SIMD; 2 = one wave per SIMD measured 2.5 % slower on the step)
- *   knob_lay22_min_nt [2]   wave-grid layouts (16-bit storage) for output tiles of at least this many 32-channel blocks
+ *   use_fused_convout [1]   honour train = 2 (output conv forward + backward as one kernel; 16-bit)
+ *   use_convout_stream [1]  128-pixel-wide images take the row-streaming form of that kernel; 0 the tiled one
+ *   use_fused_wgrad [1]     one pass over (dz, y) for the input AND weight gradient of final_layer.0 / decoder.2 / encoder.1 (16-bit):
+ *                           1 all three, 2 the transposed-conv layers final_layer.0 / decoder.2 only, 3 encoder.1 only, anything else none
+ *   use_recomp_dz [0]       final_layer.0's dz recomputed from dlogit instead of stored.  Bit-identical and 268 MB less traffic each
+ *                           way, but measured SLOWER (1.50 vs 1.33 ms/step): the per-element BatchNorm-backward in accumulator layout
+ *                           costs ~20 VALU per element, and the output-conv backward is VALU-bound, not write-bound (134 us without
+ *                           the store, 128 us with it).  Kept for the day both epilogues are cheap.
+ *   use_raw_wgrad [0]       deep layers' weight gradients read MATERIALISED operands (LeakyReLU(BN(y)) / the BatchNorm-backward gradient,
+ *                           written as a side effect by the kernel that stages them first) as plain copies.  Bit-identical; measured
+ *                           1 % SLOWER in the step (the extra stores cost the chain more than the weight-gradient kernels gain)
+ *   use_deep [1]            workgroup-specialised kernels of the deep layers: bit 0 stride-2 conv products, bit 1 transposed products.
+ *                           Three runs each: bit 0 alone 1.262 ms/step, neither 1.267, both 1.279, bit 1 alone 1.279 - the transposed
+ *                           kernel's nine LDS-DMA issues per consumer wave and K step (~130 cycles each) cost what its overlap wins
+ *   use_latent_mfma [6]     skinny linears around the latent on the exact-f32 MFMA, one 64-feature tile x the whole batch per workgroup,
+ *                           no batch split / slabs / reduction launches.  Bits: 1 decoder_input forward, 2 its weight + bias gradient,
+ *                           4 fc_mu|fc_var weight (+ bias) gradient, 8 fc input gradient.  Isolated: weight gradients 22 / 26 us against
+ *                           30 / 28 us + 4 reductions (26 us); the forward (14 vs 12 us) and the fc input gradient (24 vs 22 us) are
+ *                           not faster and stay on the VALU kernels - whose summation order the f32 parity gates were measured with
+ *   use_dnf_stream [1]      encoder.1 forward on 128x128 images: row-streaming kernel; 0 the tiled one
+ *   use_upf_stream [1]      row-streaming transposed-conv forward on 128x128 images: bit 0 final_layer.0, bit 1 decoder.2 (measures the
+ *                           same 32 us as the tiled kernel); 0 the tiled kernels
+ *   use_fc_dgrad8 [1]       fc input gradient, 16-bit: 8 channels x 4 rows per thread with 16-byte accesses (bit 1: 512-thread
+ *                           workgroups over 64 rows for batches above 32); 0 one channel per thread
+ *   use_wgrad_split [1]     deep weight gradients: producer / consumer wave groups; 0 the 8-wave kernel
+ * Grid / tile sizing:
+ *   knob_up_per_cu [2]      resident workgroups per CU of the transposed-conv kernels: 2 beats 4 by 2 % of the step, 1 and 3 are worse
+ *   knob_down_per_cu [2]    the same for the stride-2 conv kernels (measured flat 1-4; at least 1)
+ *   knob_bwd_per_cu [0]     cap on both for backward launches (0: none)
+ *   knob_nt_max [4]         output channels per workgroup tile of the pipelined kernels, in 32-channel blocks
+ *   knob_up_nt_max [1]      the same for the transposed-conv kernels (1: more, smaller workgroups at two waves per SIMD; 2 = one wave
+ *                           per SIMD measured 2.5 % slower on the step; at least 1)
+ *   knob_wave_nt_max [4]    wave-independent tiles for output tiles of up to this many 32-channel blocks
+ *   knob_lay22_min_nt [2]   wave-grid layouts (16-bit) for output tiles of at least this many 32-channel blocks
+ *   knob_down_waves [8]     waves of the wide stride-2 conv kernels: 8 = 2x4 wave grid on 128-channel tiles and 4x2 on 64-channel
+ *                           tiles, 4 = 2x2
+ *   knob_lay42 [1]          0: no 4x2 wave grid on 64-channel tiles (they take the 2x2 one)
+ *   knob_pipe_max_cout [256]  the pipelined kernels take layers of up to this many output channels
+ *   knob_xcd_map [1]        persistent workgroups walk a contiguous range of work items per XCD; applied where the grid is a
+ *                           multiple of 8 and each XCD's share of it a multiple of the output-channel tiles (else, and with 0: interleaved)
  *   knob_rev [4]            reverse tile walk (bit 0 output-conv forward, 1 output-conv backward, 2 backward conv kernels,
  *                           3 weight-gradient kernels, 4 forward conv kernels, 5 alternate per launch): a consumer that starts with
  *                           what its producer wrote last finds it in L2 / the memory-side cache
- *   knob_wgrad_mid8 [0]     eight waves on the 64x32-channel weight-gradient tile (measured slower; diagnostics)
- *   knob_wgrad_force_simple [0]  take the 64-bit-offset weight-gradient kernel (the fallback for tensors >= 4 GiB) at any size
  *   knob_lean [1]           launches kept off the critical chain (bit 0 reparameterisation noise drawn beside the first conv,
  *                           1 BatchNorm backward of encoder block 0 inside its weight-gradient kernel, 2 vae_loss_deferred
  *                           really on a side stream)
- *   knob_wave_nt_max [4]    wave-independent tiles for output tiles of up to this many 32-channel blocks
- *   knob_nt_max [4], knob_up_per_cu [2] (resident workgroups per CU of the transposed-conv kernels: 2 beats 4 by 2 % of the step, 1 and 3 are worse), knob_down_per_cu [2] (measured flat 1-4), knob_convout_grid [1536], knob_convout_bwd_grid [1024] (persistent workgroups of the output-conv forward / backward kernels; full rounds of what is resident - 768 / 512 - beat 2048 by 1 %; the backward grid equals knob_convout_step_grid so that both partition the tiles alike), knob_pipe_max_cout [256], knob_bwd_per_cu [0],
- *   knob_wgrad_tile [1], knob_wgrad_wide [1], knob_wgrad_wgs [128], knob_wgrad_wide_wgs [128], knob_wgrad_cap_mb [48],
- *   knob_conv1_grid [1024], knob_pack_grid [128], knob_ablate_b [0]   grid / tile sizing
- *   knob_wgrad_layer_wgs [0]  diagnostic: (layer mask << 16) | workgroups overrides the weight-gradient split of the masked layers
- *   knob_skip_wgrad [0], knob_ablate_f [0]      ablation diagnostics (skip weight-gradient launches by layer mask / phases
- *                           of the encoder.1 fused kernel): results are WRONG when set - timing experiments only */
+ *   knob_pack_grid [128]    workgroups per tensor of the weight-packing kernel (at least 1)
+ *   knob_conv1_grid [512]   most workgroups of encoder.0's forward (few workgroups: one f64 atomic per channel each)
+ *   knob_fused_grid [256]   persistent workgroups of the use_fused_wgrad kernels (clamped to 1..512)
+ *   knob_convout_grid [1536]  persistent workgroups of the output-conv forward kernel, and
+ *   knob_convout_bwd_grid [1024]  of its backward kernel: full rounds of what is resident - 768 / 512 - beat 2048 by 1 %
+ *   knob_convout_step_grid [1024]  of the fused (train = 2) kernel (swept 512-4096: 1.328 / 1.323 / 1.334 / 1.341 / 1.354 ms; at
+ *                           least 1).  Equal to the backward grid so that both partition the tiles alike: bit-identical statistics
+ *   knob_convout_bands [0]  bands per image of the row-streaming output-conv kernel (0: chosen by the launcher)
+ *   knob_wgrad_tile [1]     weight-gradient channel tile: 1 = 64x32 also where 64x64 would fit (0), 2 = 32x32
+ *   knob_wgrad_wide [1]     128x32-channel tiles on 8 waves where the low-res side has >= 128 channels (16-bit)
+ *   knob_wgrad_wgs [128]    split-K workgroup target of the weight gradients on a saturated GPU (at most 1024), and
+ *   knob_wgrad_wide_wgs [128]  the same for the wide tile: few workgroups keep them out of the input-gradient chain's way (-4 % step time)
+ *   knob_wgrad_cap_mb [48]  bound on a layer's split-K slab traffic, MiB (at most 48: the slabs are sized at vae_create)
+ *   knob_wgrad_mid8 [0]     eight waves on the 64x32-channel weight-gradient tile (measured slower; diagnostics)
+ * Diagnostics:
+ *   knob_wgrad_force_simple [0]  take the 64-bit-offset weight-gradient kernel (the fallback for tensors >= 4 GiB) at any size
+ *   knob_wgrad_layer_wgs [0]  (layer mask << 16) | workgroups overrides the weight-gradient split of the masked layers
+ *   knob_ablate_b [0]       the pipelined conv kernels skip their weight-fragment reloads (and take the deep layers too: the
+ *                           workgroup-specialised kernels of use_deep are off while it is set),
+ *   knob_skip_wgrad [0]     bit i skips the separate weight-gradient launch of BatchNorm layer i, and
+ *   knob_ablate_f [0]       phase ablation of the fused kernels: results are WRONG when any of the three is set - timing experiments only */
 int vae_set_option(vae_ctx* ctx, const char* name, int value);
+/* The option list itself, without a context: name and default (as above) of option `index`; 0, or -1 past either end. */
+int vae_option_info(int index, const char** name, int* default_value);
 
 #ifdef __cplusplus
 }

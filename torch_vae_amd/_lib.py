@@ -110,6 +110,7 @@ def lib():
     _sig(L.vae_debug_tensor, i32, [p, i32, p, i64, p])
     _sig(L.vae_selftest_tr16, i32, [p])
     _sig(L.vae_set_option, i32, [p, C.c_char_p, i32])
+    _sig(L.vae_option_info, i32, [i32, C.POINTER(C.c_char_p), C.POINTER(C.c_int)])
     _lib = L
     return L
 
@@ -122,7 +123,7 @@ EXPORTS = [
     "vae_comm_destroy", "vae_allreduce_grads", "vae_broadcast_state", "vae_adamw_step", "vae_train_step", "vae_train_step_fused",
     "vae_grad_norm", "vae_adamw_step_clipped", "vae_train_step_fused_clipped", "vae_synth_pianoroll", "vae_expand_stimuli", "vae_profile",
     "vae_profile_report", "vae_profile_sequence", "vae_profile_timeline", "vae_debug_stamps", "vae_debug_tensor",
-    "vae_selftest_tr16", "vae_set_option",
+    "vae_selftest_tr16", "vae_set_option", "vae_option_info",
 ]
 
 

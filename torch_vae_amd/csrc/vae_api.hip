@@ -99,14 +99,49 @@ extern "C" void vae_destroy(vae_ctx* c) {
 }
 extern "C" int64_t vae_workspace_bytes(const vae_ctx* c) { return c ? c->ws_bytes : 0; }
 
+// ---- tuning / diagnostic switches ------------------------------------------------------------------------------------------
+// One row per option: name, the int it controls, the default and the normaliser applied on set - the default is in set-value
+// terms, i.e. the value that, passed to vae_set_option, restores the default behaviour.  vae_create and vae_set_option go through
+// this table and nothing else does: the members are plain ints read directly where a launch is shaped.  What each option does is
+// documented at vae_set_option in include/vae_step.h (tests/test_options_host.py holds the two lists together).
+struct OptionDef { const char* name; int& (*ref)(vae_ctx&); int def; int (*norm)(int); };
+static int opt_any(int v) { return v; }
+static int opt_min1(int v) { return std::max(1, v); }
+static int opt_fused_grid(int v) { return std::max(1, std::min(v, 512)); }   // the fused kernels' slabs hold 512 workgroups
+static int opt_max1024(int v) { return std::min(v, 1024); }
+static int opt_max48(int v) { return std::min(v, 48); }                      // the slabs are sized for 48 MiB per layer at vae_create
+static int opt_fused_wgrad(int v) { return v == 1 ? 3 : v == 2 ? 1 : v == 3 ? 2 : 0; }   // 1 all, 2 decoder side only, 3 encoder.1 only -> bit 0 decoder (ConvT) kernels, bit 1 encoder.1 kernel
+#define OPT(member, def, norm) {#member, [](vae_ctx& c) -> int& { return c.member; }, def, norm}
+#define OPT_WK(member, def, norm) {"knob_wgrad_" #member, [](vae_ctx& c) -> int& { return c.wk.member; }, def, norm}
+static const OptionDef kOptions[] = {
+    OPT(use_tr16, 1, opt_any), OPT(use_mfma_convout, 1, opt_any), OPT(use_pipelined, 1, opt_any), OPT(use_side_stream, 1, opt_any),
+    OPT(use_fused_bn, 1, opt_any), OPT(use_fused_convout, 1, opt_any), OPT(use_fused_wgrad, 1, opt_fused_wgrad), OPT(use_recomp_dz, 0, opt_any),
+    OPT(use_raw_wgrad, 0, opt_any), OPT(use_deep, 1, opt_any), OPT(use_latent_mfma, 6, opt_any), OPT(use_convout_stream, 1, opt_any),
+    OPT(use_dnf_stream, 1, opt_any), OPT(use_upf_stream, 1, opt_any), OPT(use_fc_dgrad8, 1, opt_any), OPT(use_wgrad_split, 1, opt_any),
+    OPT(knob_up_per_cu, 2, opt_any), OPT(knob_down_per_cu, 2, opt_min1), OPT(knob_bwd_per_cu, 0, opt_any), OPT(knob_nt_max, 4, opt_any),
+    OPT(knob_up_nt_max, 1, opt_min1), OPT(knob_wave_nt_max, 4, opt_any), OPT(knob_lay22_min_nt, 2, opt_any), OPT(knob_lay42, 1, opt_any),
+    OPT(knob_down_waves, 8, opt_any), OPT(knob_pipe_max_cout, 256, opt_any), OPT(knob_xcd_map, 1, opt_any), OPT(knob_rev, 4, opt_any),
+    OPT(knob_lean, 1, opt_any), OPT(knob_pack_grid, 128, opt_min1), OPT(knob_conv1_grid, 512, opt_any), OPT(knob_fused_grid, 256, opt_fused_grid),
+    OPT(knob_convout_grid, 1536, opt_any), OPT(knob_convout_bwd_grid, 1024, opt_any), OPT(knob_convout_step_grid, 1024, opt_min1),
+    OPT(knob_convout_bands, 0, opt_any), OPT(knob_wgrad_layer_wgs, 0, opt_any), OPT(knob_skip_wgrad, 0, opt_any), OPT(knob_ablate_b, 0, opt_any),
+    OPT(knob_ablate_f, 0, opt_any),
+    OPT_WK(tile, 1, opt_any), OPT_WK(wide, 1, opt_any), OPT_WK(mid8, 0, opt_any), OPT_WK(force_simple, 0, opt_any),
+    OPT_WK(wgs, 128, opt_max1024), OPT_WK(wide_wgs, 128, opt_max1024), OPT_WK(cap_mb, 48, opt_max48),
+};
+#undef OPT_WK
+#undef OPT
+static const OptionDef* find_option(const char* name) {
+    for (const OptionDef& o : kOptions) if (name && !strcmp(name, o.name)) return &o;
+    return nullptr;
+}
+
 extern "C" vae_ctx* vae_create(int H, int L, int maxB, int dtype, int gen) {
     vae_ctx* c = new vae_ctx();
-    c->H = H; c->L = L; c->maxB = maxB; c->dtype = dtype; c->gen = gen; c->ws_bytes = 0; c->use_tr16 = 1; c->use_mfma_convout = 1; c->use_pipelined = 1; c->knob_up_per_cu = 2; c->knob_convout_grid = 1536; c->knob_convout_bwd_grid = 1024; c->knob_down_per_cu = 2; c->knob_nt_max = 4; c->knob_pipe_max_cout = 256; c->knob_ablate_b = 0; c->use_side_stream = 1; c->knob_bwd_per_cu = 0; c->knob_wave_nt_max = 4; c->knob_lay22_min_nt = 2; c->knob_down_waves = 8; c->knob_pack_grid = 128; c->knob_xcd_map = 1; c->knob_up_nt_max = 1; c->knob_lay42 = 1; c->knob_wgrad_layer_wgs = 0; c->knob_conv1_grid = 512; c->use_fused_bn = 1; c->knob_rev = 4; c->knob_lean = 1; c->walk_dir = 0; c->n_side_ok = 0; c->side_rr = 0; c->fork_rr = 0; c->comm_busy = 0; c->dbg_buf = nullptr; c->dbg_tag[0] = 0; c->dbg_epi = 0;
+    c->H = H; c->L = L; c->maxB = maxB; c->dtype = dtype; c->gen = gen;
+    for (const OptionDef& o : kOptions) o.ref(*c) = o.norm(o.def);
     if (getenv("VAE_NO_SIDE_STREAM")) c->use_side_stream = 0;   // diagnostics: everything on the caller's stream
-    c->packed_for = nullptr; c->bwd_dirty = 1; c->bwd_half_done = 0; c->B = 0; c->trained = 0; c->prof = 0; c->tag = nullptr;
     if (vae_param_layout(H, L, gen, c->poff, c->psz, &c->ptotal) != 0) { delete c; return nullptr; }
     if (dtype != VAE_DTYPE_F32 && dtype != VAE_DTYPE_BF16 && dtype != VAE_DTYPE_F16) { vae_set_error("vae_create", "bad dtype"); delete c; return nullptr; }
-    c->gmul = 1.f; c->ginv = 1.f; c->generic_accum = nullptr;
     if (maxB < 1) { vae_set_error("vae_create", "max_batch < 1"); delete c; return nullptr; }
     vae_bn_layout(c->bnoff, c->bnc, &c->bntotal);
     c->s = gen ? H / 16 : 2; c->s2 = c->s * c->s; c->F = 256LL * c->s2;
@@ -209,55 +244,15 @@ extern "C" vae_ctx* vae_create(int H, int L, int maxB, int dtype, int gen) {
     return c;
 }
 
+extern "C" int vae_option_info(int index, const char** name, int* default_value) {
+    if (index < 0 || index >= (int)(sizeof(kOptions) / sizeof(kOptions[0]))) return -1;
+    if (name) *name = kOptions[index].name;
+    if (default_value) *default_value = kOptions[index].def;
+    return 0;
+}
 extern "C" int vae_set_option(vae_ctx* c, const char* name, int value) {
     if (!c) return vae_set_error("vae_set_option", "null ctx");
-    if (!strcmp(name, "use_tr16")) { c->use_tr16 = value; return 0; }
-    if (!strcmp(name, "use_mfma_convout")) { c->use_mfma_convout = value; return 0; }
-    if (!strcmp(name, "use_pipelined")) { c->use_pipelined = value; return 0; }
-    if (!strcmp(name, "knob_up_per_cu")) { c->knob_up_per_cu = value; return 0; }
-    if (!strcmp(name, "knob_convout_grid")) { c->knob_convout_grid = value; return 0; }
-    if (!strcmp(name, "knob_down_per_cu")) { c->knob_down_per_cu = std::max(1, value); return 0; }
-    if (!strcmp(name, "knob_convout_bwd_grid")) { c->knob_convout_bwd_grid = value; return 0; }
-    if (!strcmp(name, "knob_nt_max")) { c->knob_nt_max = value; return 0; }
-    if (!strcmp(name, "knob_pipe_max_cout")) { c->knob_pipe_max_cout = value; return 0; }
-    if (!strcmp(name, "knob_ablate_b")) { c->knob_ablate_b = value; return 0; }
-    if (!strcmp(name, "use_side_stream")) { c->use_side_stream = value; return 0; }
-    if (!strcmp(name, "knob_bwd_per_cu")) { c->knob_bwd_per_cu = value; return 0; }
-    if (!strcmp(name, "knob_wave_nt_max")) { c->knob_wave_nt_max = value; return 0; }
-    if (!strcmp(name, "use_fused_bn")) { c->use_fused_bn = value; return 0; }
-    if (!strcmp(name, "knob_lay22_min_nt")) { c->knob_lay22_min_nt = value; return 0; }
-    if (!strcmp(name, "knob_down_waves")) { c->knob_down_waves = value; return 0; }
-    if (!strcmp(name, "knob_wgrad_layer_wgs")) { c->knob_wgrad_layer_wgs = value; return 0; }
-    if (!strcmp(name, "knob_lay42")) { c->knob_lay42 = value; return 0; }
-    if (!strcmp(name, "knob_up_nt_max")) { c->knob_up_nt_max = value < 1 ? 1 : value; return 0; }
-    if (!strcmp(name, "knob_xcd_map")) { c->knob_xcd_map = value; return 0; }
-    if (!strcmp(name, "knob_pack_grid")) { c->knob_pack_grid = value > 0 ? value : 1; return 0; }
-    if (!strcmp(name, "knob_conv1_grid")) { c->knob_conv1_grid = value; return 0; }
-    if (!strcmp(name, "knob_rev")) { c->knob_rev = value; return 0; }
-    if (!strcmp(name, "knob_lean")) { c->knob_lean = value; return 0; }   // bit 0: noise beside conv1; 1: BN backward inside conv1_wgrad; 2: deferred loss on a side stream
-    if (!strcmp(name, "use_fused_wgrad")) { c->use_fused_wgrad = value == 1 ? 3 : (value == 2 ? 1 : (value == 3 ? 2 : 0)); return 0; }   // 1 all, 2 decoder side only, 3 encoder.1 only
-    if (!strcmp(name, "use_recomp_dz")) { c->use_recomp_dz = value; return 0; }
-    if (!strcmp(name, "use_fc_dgrad8")) { c->use_fc_dgrad8 = value; return 0; }
-    if (!strcmp(name, "use_fused_convout")) { c->use_fused_convout = value; return 0; }
-    if (!strcmp(name, "use_convout_stream")) { c->use_convout_stream = value; return 0; }
-    if (!strcmp(name, "use_wgrad_split")) { c->use_wgrad_split = value; return 0; }
-    if (!strcmp(name, "use_upf_stream")) { c->use_upf_stream = value; return 0; }
-    if (!strcmp(name, "use_dnf_stream")) { c->use_dnf_stream = value; return 0; }
-    if (!strcmp(name, "knob_convout_bands")) { c->knob_convout_bands = value; return 0; }
-    if (!strcmp(name, "knob_convout_step_grid")) { c->knob_convout_step_grid = value > 0 ? value : 1; return 0; }
-    if (!strcmp(name, "knob_ablate_f")) { c->knob_ablate_f = value; return 0; }
-    if (!strcmp(name, "knob_skip_wgrad")) { c->knob_skip_wgrad = value; return 0; }
-    if (!strcmp(name, "use_raw_wgrad")) { c->use_raw_wgrad = value; return 0; }
-    if (!strcmp(name, "use_deep")) { c->use_deep = value; return 0; }
-    if (!strcmp(name, "use_latent_mfma")) { c->use_latent_mfma = value; return 0; }
-    if (!strcmp(name, "knob_fused_grid")) { c->knob_fused_grid = std::max(1, std::min(value, 512)); return 0; }
-    if (!strcmp(name, "knob_wgrad_tile")) { c->wk.tile = value; return 0; }
-    if (!strcmp(name, "knob_wgrad_wide")) { c->wk.wide = value; return 0; }
-    if (!strcmp(name, "knob_wgrad_mid8")) { c->wk.mid8 = value; return 0; }
-    if (!strcmp(name, "knob_wgrad_force_simple")) { c->wk.force_simple = value; return 0; }   // diagnostics: the 64-bit-offset fallback kernel
-    if (!strcmp(name, "knob_wgrad_wide_wgs")) { c->wk.wide_wgs = std::min(value, 1024); return 0; }
-    if (!strcmp(name, "knob_wgrad_wgs")) { c->wk.wgs = std::min(value, 1024); return 0; }
-    if (!strcmp(name, "knob_wgrad_cap_mb")) { c->wk.cap_mb = std::min(value, 48); return 0; }
+    if (const OptionDef* o = find_option(name)) { o->ref(*c) = o->norm(value); return 0; }
     return vae_set_error("vae_set_option", "unknown option");
 }
 SideFork fork_side(vae_ctx* c, hipStream_t st, int which) {
@@ -369,10 +364,11 @@ extern "C" int vae_forward(vae_ctx* c, const float* x, int B, const float* param
     if (B < 1 || B > c->maxB) return vae_set_error("vae_forward", "batch exceeds the context's max_batch");
     if (!x || !params || !xhat || !mu || !lv || !z) return vae_set_error("vae_forward", "null tensor pointer");
     hipStream_t st = (hipStream_t)stream;
-    c->cur_stream = st; c->cur_stream_set = true;
-    c->fwd_recon = c->recon;
-    c->fwd_kl_kind = c->kl_kind; c->fwd_kl_param = c->kl_param; c->kl_pending = 0;
-    return VAE_DISPATCH(c->dtype, forward_impl, (c, x, B, params, bn_running, nbt, eps, seed, train, xhat, mu, lv, z, st));
+    if (begin_forward(c, FwdRecord::FULL, B, train, st)) return -1;
+    c->fwd.x = x; c->fwd.xhat = xhat; c->fwd.mu = mu; c->fwd.lv = lv; c->fwd.z = z;
+    const int rc = VAE_DISPATCH(c->dtype, forward_impl, (c, x, B, params, bn_running, nbt, eps, seed, train, xhat, mu, lv, z, st));
+    if (rc) drop_forward(c);
+    return rc;
 }
 
 extern "C" int vae_decode(vae_ctx* c, const float* z, int B, const float* params, float* bn_running, int64_t* nbt, int train,
@@ -381,18 +377,13 @@ extern "C" int vae_decode(vae_ctx* c, const float* z, int B, const float* params
     if (B < 1 || B > c->maxB) return vae_set_error("vae_decode", "batch exceeds the context's max_batch");
     if (!z || !params || !xhat) return vae_set_error("vae_decode", "null tensor pointer");
     hipStream_t st = (hipStream_t)stream;
-    c->cur_stream = st; c->cur_stream_set = true;
-    // what vae_backward_ex needs of a decode-only pass (its BatchNorm mode, z, xhat, the gradient scale); vae_backward refuses it
-    c->B = B; c->trained = train; c->fwd_kind = 2; c->fwd_recon = c->recon;   // (c->B: the batch statistics' count)
-    c->fwd_kl_kind = VAE_KL_PLAIN; c->kl_pending = 0;
-    c->x = xhat; c->xhat = xhat; c->z = const_cast<float*>(z); c->mu = c->lv = nullptr;
-    set_grad_scale(c, B);
-    HIP_CHECK_RET(hipMemsetAsync(c->dstats, 0, c->n_dstats * sizeof(double), st)); c->bwd_dirty = 0;
+    // what vae_backward_ex needs of a decode-only pass: its BatchNorm mode, z, xhat, the gradient scale; vae_backward refuses it
+    if (begin_forward(c, FwdRecord::DECODE, B, train, st)) return -1;
+    c->fwd.x = xhat; c->fwd.xhat = xhat; c->fwd.z = const_cast<float*>(z);
     int rc = VAE_DISPATCH(c->dtype, pack_weights, (c, params, st));
-    if (rc) { c->B = 0; return rc; }
     // the reconstruction-loss side outputs of the output-conv kernel are unused here: xhat doubles as the target
-    rc = VAE_DISPATCH(c->dtype, decode_impl, (c, z, B, params, bn_running, nbt, train, xhat, xhat, st));
-    if (rc) c->B = 0;
+    if (!rc) rc = VAE_DISPATCH(c->dtype, decode_impl, (c, z, B, params, bn_running, nbt, train, xhat, xhat, st));
+    if (rc) drop_forward(c);
     return rc;
 }
 
@@ -402,11 +393,10 @@ extern "C" int vae_encode(vae_ctx* c, const float* x, int B, const float* params
     if (B < 1 || B > c->maxB) return vae_set_error("vae_encode", "batch exceeds the context's max_batch");
     if (!x || !params || !mu || !lv || !z) return vae_set_error("vae_encode", "null tensor pointer");
     hipStream_t st = (hipStream_t)stream;
-    c->cur_stream = st; c->cur_stream_set = true;
-    c->fwd_recon = c->recon; c->xhat = nullptr; c->dlogit_valid = 0; c->convout_pending = 0;
-    c->fwd_kind = 1; c->fwd_kl_kind = VAE_KL_PLAIN; c->kl_pending = 0;   // (no ELBO follows an encoder-only pass)
+    if (begin_forward(c, FwdRecord::ENCODE, B, train, st)) return -1;
+    c->fwd.x = x; c->fwd.mu = mu; c->fwd.lv = lv; c->fwd.z = z;
     const int rc = VAE_DISPATCH(c->dtype, encode_impl, (c, x, B, params, bn_running, nbt, eps, seed, train, mu, lv, z, st));
-    if (rc) c->B = 0;
+    if (rc) drop_forward(c);
     return rc;
 }
 
@@ -438,14 +428,14 @@ extern "C" int vae_log_likelihood(vae_ctx* c, const float* x, int B, const float
     }
     float* mu = c->ll_f; float* lv = mu + maxB * L; float* z0 = lv + maxB * L; float* zc = z0 + maxB * L;
     double* lpx = c->ll_kb; double* lw = log_w ? log_w : c->ll_kb + kb;
-    // whatever happens below, the context is left without a forward to differentiate or score
-    struct Reset { vae_ctx* c; ~Reset() { c->ps_part = nullptr; c->B = 0; c->trained = 0; c->dlogit_valid = 0; c->convout_pending = 0; } } reset{c};
-    c->cur_stream = st; c->cur_stream_set = true;
-    c->fwd_recon = c->recon; c->fwd_kl_kind = VAE_KL_PLAIN; c->kl_pending = 0;
+    // an eval-mode encoder pass with decoder passes on top; whatever happens below, the context is left without a forward
+    struct Drop { vae_ctx* c; ~Drop() { drop_forward(c); } } drop{c};
+    if (begin_forward(c, FwdRecord::ENCODE, B, 0, st)) return -1;
+    c->fwd.x = x; c->fwd.mu = mu; c->fwd.lv = lv; c->fwd.z = z0;
     float* bnr = const_cast<float*>(bn_running);   // eval mode: read only
     int rc = VAE_DISPATCH(c->dtype, encode_impl, (c, x, B, params, bnr, nullptr, nullptr, seed, 0, mu, lv, z0, st));
     if (rc) return rc;
-    const double cst = c->fwd_recon == VAE_RECON_MSE ? 0.5 * H * H * log(3.14159265358979323846) : 0.0;
+    const double cst = c->fwd.recon == VAE_RECON_MSE ? 0.5 * H * H * log(3.14159265358979323846) : 0.0;
     for (int k0 = 0; k0 < K; k0 += chunk) {
         const int nk = std::min(chunk, K - k0), R = nk * B;
         IwLatentArgs la; la.mu = mu; la.lv = lv; la.eps = eps; la.z = zc; la.lat = c->ll_lat; la.B = B; la.L = L; la.k0 = k0; la.nk = nk;
@@ -511,51 +501,53 @@ int launch_kl_shape(vae_ctx* c, hipStream_t st) {
     SideFork f = fork_side(c, st, vae_ctx::KL_SIDE);
     if (f.rc) return f.rc;
     {
-        ProfScope ps(c, "kl_shape", 8.0 * c->B * c->L + 12.0 * c->L, 0, f.st);
-        if (enqueue_kl_shape(c->mu, c->lv, c->B, c->L, c->fwd_kl_kind, c->fwd_kl_param, c->kl_d(), c->kl_scal(), c->kl_factor(), c->kl_tk, f.st)) return -1;
+        ProfScope ps(c, "kl_shape", 8.0 * c->fwd.B * c->L + 12.0 * c->L, 0, f.st);
+        if (enqueue_kl_shape(c->fwd.mu, c->fwd.lv, c->fwd.B, c->L, c->fwd.kl_kind, c->fwd.kl_param, c->kl_d(), c->kl_scal(), c->kl_factor(), c->kl_tk, f.st)) return -1;
     }
     HIP_CHECK_RET(hipEventRecord(c->ev_kl, f.st));
-    c->kl_pending = 1;
+    c->fwd.kl_pending = 1;
     return 0;
 }
 int join_kl(vae_ctx* c, hipStream_t st) {
-    if (c->kl_pending) HIP_CHECK_RET(hipStreamWaitEvent(st, c->ev_kl, 0));
+    if (c->fwd.kl_pending) HIP_CHECK_RET(hipStreamWaitEvent(st, c->ev_kl, 0));
     return 0;
 }
 extern "C" int vae_kl_per_dim(vae_ctx* c, double* out, vae_stream_t stream) {
-    if (!c || !c->B || !c->mu || !c->lv) return vae_set_error("vae_kl_per_dim", "no forward with a posterior (vae_forward, a training step or vae_encode)");
+    if (!c || !c->fwd || !c->fwd.mu || !c->fwd.lv) return vae_set_error("vae_kl_per_dim", "no forward with a posterior (vae_forward, a training step or vae_encode)");
     if (!out) return vae_set_error("vae_kl_per_dim", "null output pointer");
     hipStream_t st = (hipStream_t)stream;
-    if (!c->kl_pending && launch_kl_shape(c, st)) return -1;   // (the forward was plain: reduce now)
+    if (!c->fwd.kl_pending && launch_kl_shape(c, st)) return -1;   // (the forward was plain: reduce now)
     if (join_kl(c, st)) return -1;
     HIP_CHECK_RET(hipMemcpyAsync(out, c->kl_d(), (size_t)c->L * 8, hipMemcpyDeviceToDevice, st));
     return 0;
 }
 
-extern "C" int vae_loss(vae_ctx* c, float kld_weight, float* out3, vae_stream_t stream) {
-    if (!c || !c->B) return vae_set_error("vae_loss", "no forward");
-    if (c->convout_pending) return vae_set_error("vae_loss", "the forward ran with train = 2: the ELBO is produced by the backward (use vae_loss_deferred)");
-    if (join_kl(c, (hipStream_t)stream)) return -1;
-    hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, c->accum, out3,
-                       1.0 / ((double)c->B * c->H * c->H), 1.0 / (double)c->B, kld_weight, STAT_R, c->kl_shaped());
+// the ELBO scalars {loss, reconstruction, -KL} of the last forward from the context's accumulators (a shaped KL objective: after join_kl)
+int launch_loss_finalize(vae_ctx* c, float* out3, float kld_weight, hipStream_t st) {
+    hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, st, c->accum, out3, 1.0 / ((double)c->fwd.B * c->H * c->H),
+                       1.0 / (double)c->fwd.B, kld_weight, STAT_R, c->kl_shaped());
     LAUNCH_CHECK("loss_finalize_kernel");
     return 0;
+}
+
+extern "C" int vae_loss(vae_ctx* c, float kld_weight, float* out3, vae_stream_t stream) {
+    if (!c || !c->fwd) return vae_set_error("vae_loss", "no forward");
+    if (c->fwd.convout_pending) return vae_set_error("vae_loss", "the forward ran with train = 2: the ELBO is produced by the backward (use vae_loss_deferred)");
+    if (join_kl(c, (hipStream_t)stream)) return -1;
+    return launch_loss_finalize(c, out3, kld_weight, (hipStream_t)stream);
 }
 
 // Same scalars, computed beside the backward instead of in front of it: enqueued on one of the context's side streams
 // (ordered after `stream`), so out3 is ordered into the caller's stream by the NEXT vae_backward / vae_backward_part
 // on this context - for callers that only read the ELBO after the backward (train.py:644-674 reads it after the step).
 extern "C" int vae_loss_deferred(vae_ctx* c, float kld_weight, float* out3, vae_stream_t stream) {
-    if (!c || !c->B) return vae_set_error("vae_loss_deferred", "no forward");
-    if (!c->trained || c->fwd_kind) return vae_set_error("vae_loss_deferred", "needs a train-mode forward (a backward must follow)");
-    if (c->convout_pending) { c->loss_out3 = out3; c->loss_kw = kld_weight; return 0; }   // finalised by the backward, after the fused output-conv kernel
+    if (!c || !c->fwd) return vae_set_error("vae_loss_deferred", "no forward");
+    if (!c->fwd.trained || c->fwd.kind != FwdRecord::FULL) return vae_set_error("vae_loss_deferred", "needs a train-mode forward (a backward must follow)");
+    if (c->fwd.convout_pending) { c->fwd.loss_out3 = out3; c->fwd.loss_kw = kld_weight; return 0; }   // finalised by the backward, after the fused output-conv kernel
     SideFork f = (c->knob_lean & 4) ? fork_side(c, (hipStream_t)stream) : SideFork{(hipStream_t)stream, c->slab, 0};
     if (f.rc) return f.rc;
     if (c->kl_shaped() && join_kl(c, f.st)) return -1;
-    hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, f.st, c->accum, out3,
-                       1.0 / ((double)c->B * c->H * c->H), 1.0 / (double)c->B, kld_weight, STAT_R, c->kl_shaped());
-    LAUNCH_CHECK("loss_finalize_kernel");
-    return 0;
+    return launch_loss_finalize(c, out3, kld_weight, f.st);
 }
 
 // Accumulators of vae_elbo_generic: the entry point has no context, so they live in a per-device ring (one slot per call:
@@ -714,16 +706,16 @@ extern "C" int vae_backward_part(vae_ctx* c, const float* x, const float* params
     if (!c) return vae_set_error("vae_backward", "null ctx");
     if (!x || !params || !grads) return vae_set_error("vae_backward", "null tensor pointer");
     hipStream_t st = (hipStream_t)stream;
-    c->cur_stream = st; c->cur_stream_set = true;
+    enter(c, st);
     return VAE_DISPATCH(c->dtype, backward_impl, (c, x, params, grads, g_xhat, gscale, g_mu, g_lv, g_z, g_pre, kld_weight, add_kl, part, st));
 }
 extern "C" int vae_backward_ex(vae_ctx* c, const float* x, const float* params, float* grads, const float* g_xhat, const float* gscale,
                                const float* g_mu, const float* g_lv, const float* g_z, const float* g_pre, float kld_weight, int add_kl,
                                float* dx, float* dz, vae_stream_t stream) {
     if (!c) return vae_set_error("vae_backward_ex", "null ctx");
-    if (!params || !grads || (!x && c->fwd_kind != 2)) return vae_set_error("vae_backward_ex", "null tensor pointer");
+    if (!params || !grads || (!x && c->fwd.kind != FwdRecord::DECODE)) return vae_set_error("vae_backward_ex", "null tensor pointer");
     hipStream_t st = (hipStream_t)stream;
-    c->cur_stream = st; c->cur_stream_set = true;
+    enter(c, st);
     return VAE_DISPATCH(c->dtype, backward_ex_impl, (c, x, params, grads, g_xhat, gscale, g_mu, g_lv, g_z, g_pre, kld_weight, add_kl, dx, dz, st));
 }
 extern "C" int vae_backward(vae_ctx* c, const float* x, const float* params, float* grads, const float* g_xhat, const float* gscale,
@@ -994,26 +986,26 @@ extern "C" int vae_profile_timeline(vae_ctx* c, char* buf, int64_t cap) {
 }
 
 extern "C" int vae_pre_latents(vae_ctx* c, float* out, vae_stream_t stream) {
-    if (!c || !c->B) return vae_set_error("vae_pre_latents", "no forward");
+    if (!c || !c->fwd) return vae_set_error("vae_pre_latents", "no forward");
     return VAE_DISPATCH(c->dtype, pre_latents_impl, (c, out, (hipStream_t)stream));
 }
 extern "C" int vae_last_eps(vae_ctx* c, float* out, vae_stream_t stream) {
-    if (!c || !c->B) return vae_set_error("vae_last_eps", "no forward");
-    HIP_CHECK_RET(hipMemcpyAsync(out, c->eps, (size_t)c->B * c->L * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (!c || !c->fwd) return vae_set_error("vae_last_eps", "no forward");
+    HIP_CHECK_RET(hipMemcpyAsync(out, c->eps, (size_t)c->fwd.B * c->L * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
 }
 
 extern "C" int vae_debug_tensor(vae_ctx* c, int which, float* out, int64_t capacity, vae_stream_t stream) {
-    if (!c || !c->B) return vae_set_error("vae_debug_tensor", "no forward");
+    if (!c || !c->fwd) return vae_set_error("vae_debug_tensor", "no forward");
     const void* src; int C, HW;
     if (which == 18) {   // the latent gradient [B, 2L] f32: no layout to convert
-        const long n = (long)c->B * 2 * c->L;
+        const long n = (long)c->fwd.B * 2 * c->L;
         if (n > capacity) return vae_set_error("vae_debug_tensor", "output too small");
         HIP_CHECK_RET(hipMemcpyAsync(out, c->dlat, (size_t)n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
         return 0;
     }
     if (which == 19) {   // the per-dimension factors of the last forward's KL objective [L] f32 (an objective other than plain)
-        if (c->fwd_kl_kind == VAE_KL_PLAIN || !c->kl_pending) return vae_set_error("vae_debug_tensor", "the last forward ran with the plain KL objective");
+        if (c->fwd.kl_kind == VAE_KL_PLAIN || !c->fwd.kl_pending) return vae_set_error("vae_debug_tensor", "the last forward ran with the plain KL objective");
         if (c->L > capacity) return vae_set_error("vae_debug_tensor", "output too small");
         if (join_kl(c, (hipStream_t)stream)) return -1;
         HIP_CHECK_RET(hipMemcpyAsync(out, c->kl_factor(), (size_t)c->L * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
@@ -1022,7 +1014,7 @@ extern "C" int vae_debug_tensor(vae_ctx* c, int which, float* out, int64_t capac
     if (which >= 0 && which < 16) { const BnLayer& l = c->lay[which & 7]; src = which < 8 ? l.y : l.dz; C = l.C; HW = l.H * l.W; }
     else if (which == 16 || which == 17) { src = which == 16 ? c->d0 : c->dd0; C = 256; HW = c->s2; }
     else return vae_set_error("vae_debug_tensor", "bad tensor id");
-    const long n = (long)c->B * C * HW;
+    const long n = (long)c->fwd.B * C * HW;
     if (n > capacity) return vae_set_error("vae_debug_tensor", "output too small");
     return VAE_DISPATCH(c->dtype, debug_tensor_impl, (c, src, out, n, C, HW, (hipStream_t)stream));
 }

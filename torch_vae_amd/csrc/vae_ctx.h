@@ -22,6 +22,7 @@ int vae_set_error(const char* what, const char* why);   // vae_api.hip; message 
     } while (0)
 
 static const int kBnC[8] = {32, 64, 128, 256, 128, 64, 32, 32};
+static const char* const kLayerTag[8] = {"encoder.0", "encoder.1", "encoder.2", "encoder.3", "decoder.0", "decoder.1", "decoder.2", "final_layer.0"};   // profiling / debug tag of BN layer i
 static const float kSlope = 0.01f;   // nn.LeakyReLU() default (models.py:47,70,79)
 static const float kBnEps = 1e-5f;   // nn.BatchNorm2d default eps
 static const float kBnMom = 0.1f;    // nn.BatchNorm2d default momentum
@@ -53,99 +54,92 @@ struct PackDesc {
     long n;       // elements of dst
 };
 
-// split-K sizing of the weight-gradient kernels (vae_set_option knobs; slabs are sized at vae_create for the defaults).
-// Workgroup targets: weight gradients run beside the input-gradient chain; on a saturated GPU (large batch x image) few
-// workgroups keep them out of its way (-4 % step time at the bench workload), a small problem wants them everywhere.
-//   wide: 128x32-channel tiles on 8 waves where the low-res side has >= 128 channels (16-bit prefetching kernel)
-//   tile 1: 64x32 channel tiles (prefetching kernel) also where 64x64 would fit
-struct WgradKnobs { int wgs = 128, cap_mb = 48, tile = 1, wide = 1, wide_wgs = 128, small_wgs = 1024, mid8 = 0, force_simple = 0; };
+// split-K sizing of the weight-gradient kernels; the slabs are sized at vae_create for the defaults.  Every member but small_wgs (the
+// workgroup target of a small problem, which wants them everywhere) is the option knob_wgrad_<member>, documented with the others
+struct WgradKnobs { int wgs, cap_mb, tile, wide, wide_wgs, small_wgs = 1024, mid8, force_simple; };
+
+// The last forward of a context: which one ran, with what settings, and what it left for vae_loss* / vae_backward* to consume.
+// Exactly two functions change which forward is held: begin_forward and drop_forward (below).  Besides them the record is written
+// where a forward's product is made or consumed: decode_impl (the output conv ran or was deferred), launch_kl_shape (kl_pending),
+// backward_first (convout_pending / dlogit_valid / loss_out3), bwd_clear_stats (bwd_dirty), backward_impl (bwd_half_done),
+// vae_loss_deferred (loss_out3 / loss_kw of a deferred output conv) and launch_conv_pipe (walk_dir).
+struct FwdRecord {
+    enum Kind { NONE, FULL, ENCODE, DECODE };   // FULL: vae_forward and the training steps; vae_backward_ex differentiates whichever it was
+    Kind kind = NONE;
+    int B = 0, trained = 0;                      // batch (the batch statistics' count); the forward's `train` argument
+    // settings the forward ran with (vae_set_recon_loss / vae_set_kl_objective at that time): its deferred output conv, loss and
+    // backward use these, whatever the context's settings are by then.  Kinds without an ELBO record VAE_KL_PLAIN.
+    int recon = VAE_RECON_BCE, kl_kind = VAE_KL_PLAIN; double kl_param = 0.0;
+    int kl_pending = 0;                          // kl_shape_kernel of this forward is in flight on side stream KL_SIDE: consumers wait for ev_kl
+    const float* x = nullptr; float *xhat = nullptr, *mu = nullptr, *lv = nullptr, *z = nullptr;   // the caller's tensors (null: the kind has none)
+    // f16 storage: the backward runs on gradients multiplied by gmul (a power of two chosen per forward so that the stored
+    // dz stay inside the f16 range: the BCE mean makes them O(1/(B*H*W))); every parameter gradient is written times ginv.
+    // The backward is linear in the upstream gradient, so this changes no f32 result (powers of two are exact).  1 otherwise.
+    float gmul = 1.f, ginv = 1.f;
+    // use_fused_convout: a forward with train = 2 (the fused training step) leaves the output conv, sigmoid and BCE to the
+    // backward, where ONE kernel does forward and backward of that layer in one pass over y7 (conv_mfma.cuh:
+    // convout_step_mfma_kernel).  convout_pending: such a forward is waiting for its backward; pending_f7: the BatchNorm
+    // finalisation that kernel's prologue performs; loss_out3 / loss_kw: where vae_loss_deferred wants the ELBO scalars.
+    // dlogit_valid: the output conv's gradient of this forward is in c->dlogit and has not been consumed.
+    int convout_pending = 0, dlogit_valid = 0; BnFuse pending_f7; float* loss_out3 = nullptr; float loss_kw = 0.f;
+    int bwd_dirty = 1;       // the backward statistics need clearing (a forward zeroes every accumulator; a backward dirties its own)
+    int bwd_half_done = 0;   // vae_backward_part 1 ran, part 2 may follow
+    int walk_dir = 0;        // knob_rev bit 5: tile-walk direction of the next pipelined launch
+    explicit operator bool() const { return kind != NONE; }
+};
 
 struct vae_ctx {
+    // ---- geometry and layouts, fixed at vae_create ----
     int H, L, maxB, dtype, gen, s, s2; int64_t F; int npad_fc, npad_di; size_t esz;
     int64_t poff[VAE_NUM_PARAMS], psz[VAE_NUM_PARAMS], ptotal, bnoff[8], bnc[8], bntotal;
+    // ---- resources: device buffers, streams, events ----
     BnLayer lay[8];
     void *d0, *dd0;
     float *eps, *dlat, *dlogit, *dlogit2, *ident, *wout_t;
     void* wp_fwd[8]; void* wp_dg[8];   // indexed by BN layer id (1..7); [0] unused
     void *fcpack, *dipack;
-    PackDesc* d_descs; std::vector<PackDesc> h_descs; const float* packed_for;
+    PackDesc* d_descs; std::vector<PackDesc> h_descs; const float* packed_for = nullptr;
     float* slab; size_t slab_floats;
     // side streams for work only the optimiser consumes (weight gradients, their split-K reductions) and for weight packing
     static constexpr int NSIDE = 3, NFORK = 16;
-    hipStream_t side[NSIDE]; float* side_slab[NSIDE]; hipEvent_t ev_fork[NFORK], ev_join[NSIDE], ev_pack; int side_rr, fork_rr, n_side_ok;
+    hipStream_t side[NSIDE]; float* side_slab[NSIDE]; hipEvent_t ev_fork[NFORK], ev_join[NSIDE], ev_pack; int side_rr = 0, fork_rr = 0, n_side_ok = 0;
     static constexpr int NBUCKET = 2; hipEvent_t ev_bucket[NBUCKET];   // bucketed gradient exchange (vae_train_step_fused): bucket i reduced on the communication stream
-    hipStream_t comm; hipEvent_t ev_comm; int comm_busy;   // stream lent to the caller for the mid-backward gradient all-reduce (vae_comm_stream)
+    hipStream_t comm; hipEvent_t ev_comm; int comm_busy = 0;   // stream lent to the caller for the mid-backward gradient all-reduce (vae_comm_stream)
     void* nccl_comm = nullptr; int comm_rank = 0, comm_world = 0;   // RCCL communicator owned by the context (vae_comm.hip)
-    int use_side_stream, knob_bwd_per_cu, knob_wave_nt_max, knob_lay22_min_nt, knob_down_waves, knob_pack_grid, knob_xcd_map, knob_up_nt_max, knob_lay42, knob_wgrad_layer_wgs, knob_conv1_grid, use_fused_bn, knob_rev, knob_lean, walk_dir, bwd_dirty, bwd_half_done;
     double* dstats; size_t n_dstats; double* accum;  // accum: [0] reconstruction term (BCE / MSE sum), [1] kl term, [2] sum dlogit
-    double* generic_accum;                           // vae_elbo_generic on this context's device (per context, not process-global)
-    WgradKnobs wk;
     float* reduce_tmp = nullptr; size_t reduce_tmp_floats = 0; unsigned reduce_slot = 0;   // partial sums of the two-level slab reduction
     float* fused_slab[3] = {nullptr, nullptr, nullptr}; size_t fused_slab_floats = 0;   // split-K slabs of the fused dgrad+wgrad kernels (layers 7, 6, 1)
-    // use_recomp_dz: final_layer.0's dz recomputed from dlogit instead of stored (conv_fused.cuh RECOMP).  Bit-identical and
-    // 268 MB less traffic each way, but measured SLOWER on MI355X (1.50 vs 1.33 ms/step): the per-element BatchNorm-backward in
-    // accumulator layout costs ~20 VALU per element, and the output-conv backward is VALU-bound, not write-bound (134 us without
-    // the store, 128 us with it).  Off by default; kept for the day both epilogues are cheap.
-    // use_raw_wgrad: deep layers' weight gradients read MATERIALISED operands (LeakyReLU(BN(y)) / BN-backward gradient written as a
-    // side effect by the kernel that stages them first) as plain copies.  Bit-identical; measured 1 % SLOWER in the step on MI355X
-    // (the extra stores cost the chain more than the weight-gradient kernels gain: their time is not in the staging arithmetic).
-    int use_raw_wgrad = 0;
-    // use_deep: workgroup-specialised kernels of the deep layers (conv_deep.cuh).  bit 0: stride-2 conv products (dn3), bit 1: transposed
-    // products (up3).  Measured on MI355X (128x128 L=16 B=256 bf16, three runs each): dn3 alone 1.262 ms/step, neither 1.267, both 1.279,
-    // up3 alone 1.279 - the transposed kernel's nine LDS-DMA issues per consumer wave and K step (~130 cycles each) cost what its
-    // overlap wins, so it is off by default.
-    int use_deep = 1;
-    // use_latent_mfma: skinny linears around the latent on the exact-f32 MFMA, one 64-feature tile x the whole batch per workgroup, no batch
-    // split / slabs / reduction launches (latent_mfma.cuh).  Bits: 1 decoder_input forward, 2 its weight + bias gradient, 4 fc_mu|fc_var weight
-    // (+ bias) gradient, 8 fc input gradient.  Measured on MI355X (128x128 L=16 B=256 bf16, isolated): weight gradients 22 / 26 us against
-    // 30 / 28 us + 4 reductions (26 us); the forward (14 vs 12 us) and the fc input gradient (24 vs 22 us) are not faster and stay on the VALU
-    // kernels - whose summation order is also the one the f32 parity gates were measured with.
-    int use_latent_mfma = 6;
-    int knob_skip_wgrad = 0;  // diagnostics: bit i skips the separate weight-gradient launch of BN layer i (results wrong, timing only)
-    int knob_ablate_f = 0;   // diagnostics: phase ablation of conv_bwd_fused_kernel (timing only)
-    // use_fused_convout: a forward with train = 2 (the fused training step) leaves the output conv, sigmoid and BCE to the
-    // backward, where ONE kernel does forward and backward of that layer in one pass over y7 (conv_mfma.cuh:
-    // convout_step_mfma_kernel).  convout_pending: such a forward is waiting for its backward; pending_f7: the BatchNorm
-    // finalisation that kernel's prologue performs; loss_out3 / loss_kw: where vae_loss_deferred wants the ELBO scalars.
-    int use_fused_convout = 1, convout_pending = 0, dlogit_valid = 0;
-    // use_convout_stream: 128-pixel-wide images take the row-streaming form of that kernel (convout_stream.cuh); 0 = the tiled one
-    int use_dnf_stream = 1;    // encoder.1 forward on 128x128 images: row-streaming kernel (dnfirst_stream.cuh); 0 = the tiled one
-    int use_upf_stream = 1;    // row-streaming transposed-conv forward on 128x128 images (upfinal_stream.cuh): bit 0 final_layer.0, bit 1 decoder.2; 0 = the tiled kernels
-    int use_fc_dgrad8 = 1;     // fc input gradient, 16-bit storage: 8 channels x 4 rows per thread with 16-byte accesses (edge_kernels.cuh: fc_dgrad8_kernel); 0 = one channel per thread
-    int use_wgrad_split = 1;   // deep weight gradients: producer / consumer wave groups (wgrad_split.cuh); 0 = the 8-wave kernel
-    int use_convout_stream = 1, knob_convout_bands = 0;   // (bands per image: 0 = chosen by the launcher)
-    int knob_convout_step_grid = 1024;   // (= knob_convout_bwd_grid: with the same tile partition the fused kernel and convout_bwd produce bit-identical statistics)
-    BnFuse pending_f7; float* loss_out3 = nullptr; float loss_kw = 0.f;
-    // reconstruction term of the ELBO (VAE_RECON_*): recon is the setting for the following forwards (vae_set_recon_loss);
-    // fwd_recon is what the last forward was run with - its deferred output conv, loss and backward use that one
-    int recon = VAE_RECON_BCE, fwd_recon = VAE_RECON_BCE;
-    // KL objective (VAE_KL_*): kl_kind / kl_param are the setting for the following forwards (vae_set_kl_objective), fwd_kl_* what
-    // the last forward recorded.  kl_ws (allocated on first use): kl_d [L] f64 | scalars {T, KL} f64 | factor [L] f32 (kl_tk: the ticket word, a 16-byte block of its own), written by
-    // kl_shape_kernel on side stream KL_SIDE; ev_kl follows it and kl_pending says that consumers of this forward must wait for it.
-    int kl_kind = VAE_KL_PLAIN, fwd_kl_kind = VAE_KL_PLAIN; double kl_param = 0.0, fwd_kl_param = 0.0;
+    // kl_ws (allocated on first use): kl_d [L] f64 | scalars {T, KL} f64 | factor [L] f32 (kl_tk: the ticket word, a 16-byte block of its
+    // own), written by kl_shape_kernel on side stream KL_SIDE; ev_kl follows it (fwd.kl_pending: consumers of this forward must wait for it)
     static constexpr int KL_SIDE = 2;
-    void* kl_ws = nullptr; unsigned* kl_tk = nullptr; hipEvent_t ev_kl = nullptr; int kl_pending = 0;
+    void* kl_ws = nullptr; unsigned* kl_tk = nullptr; hipEvent_t ev_kl = nullptr;
     unsigned long long* kl_d() const { return static_cast<unsigned long long*>(kl_ws); }
     double* kl_scal() const { return reinterpret_cast<double*>(kl_d() + L); }
     float* kl_factor() const { return reinterpret_cast<float*>(kl_scal() + 2); }
-    const double* kl_shaped() const { return fwd_kl_kind != VAE_KL_PLAIN ? kl_scal() : nullptr; }   // loss_finalize_kernel's argument
+    const double* kl_shaped() const { return fwd.kl_kind != VAE_KL_PLAIN ? kl_scal() : nullptr; }   // loss_finalize_kernel's argument
     // vae_log_likelihood: ps_part (non-null only during its decoder passes) switches the output conv to its per-sample mode
     // (tile partials, target x[b mod ps_tb]; ps_ntile: tiles per image of the kernel taken).  ll_*: its scratch, allocated on first use.
     double* ps_part = nullptr; int ps_tb = 0, ps_ntile = 0;
     float* ll_f = nullptr; double* ll_part = nullptr; double* ll_lat = nullptr;   // ll_f: mu | lv | z0 [maxB*L] | z [maxB*L]
     double* ll_kb = nullptr; size_t ll_kb_n = 0;                                   // [K*B] log p(x|z) | [K*B] log w (grown per call)
-    int use_fused_wgrad = 3, knob_fused_grid = 256, use_recomp_dz = 0;   // use_fused_wgrad: bit 0 decoder (ConvT) kernels, bit 1 encoder.1 kernel
-    // f16 storage: the backward runs on gradients multiplied by gmul (a power of two chosen per forward so that the stored
-    // dz stay inside the f16 range: the BCE mean makes them O(1/(B*H*W))); every parameter gradient is written times ginv.
-    // The backward is linear in the upstream gradient, so this changes no f32 result (powers of two are exact).  1 otherwise.
-    float gmul, ginv;
-    // last forward; fwd_kind: what it ran - 0 the whole model (vae_forward, the training steps), 1 the encoder only (vae_encode),
-    // 2 the decoder only (vae_decode); vae_backward_ex differentiates whichever it was
-    int B; int trained; int fwd_kind = 0; const float* x; float *xhat, *mu, *lv, *z;
-    int use_tr16, use_mfma_convout, use_pipelined, knob_up_per_cu, knob_convout_grid, knob_convout_bwd_grid, knob_down_per_cu, knob_nt_max, knob_pipe_max_cout, knob_ablate_b; long long* dbg_buf; char dbg_tag[32]; int dbg_epi; int64_t ws_bytes;
-    std::vector<void*> allocs;
-    // per-kernel timing (bench.py roofline): HIP events on the launch stream
-    int prof; const char* tag; struct ProfRec { std::string name; hipEvent_t e0, e1; double bytes, flops; int side; int launches = 1; }; std::vector<ProfRec> prof_recs;
+    std::vector<void*> allocs; int64_t ws_bytes = 0;
+    // ---- tuning switches: plain ints read directly where a launch is shaped.  Names, defaults and the clamps applied on set are the
+    // rows of kOptions (vae_api.hip), which vae_create and vae_set_option go through; what each one does, and what was measured with
+    // it, is documented once, at vae_set_option in include/vae_step.h ----
+    int use_tr16, use_mfma_convout, use_pipelined, use_side_stream, use_fused_bn, use_fused_convout, use_fused_wgrad, use_recomp_dz, use_raw_wgrad,
+        use_deep, use_latent_mfma, use_convout_stream, use_dnf_stream, use_upf_stream, use_fc_dgrad8, use_wgrad_split;
+    int knob_up_per_cu, knob_down_per_cu, knob_bwd_per_cu, knob_nt_max, knob_up_nt_max, knob_wave_nt_max, knob_lay22_min_nt, knob_lay42,
+        knob_down_waves, knob_pipe_max_cout, knob_xcd_map, knob_rev, knob_lean, knob_pack_grid, knob_conv1_grid, knob_fused_grid,
+        knob_convout_grid, knob_convout_bwd_grid, knob_convout_step_grid, knob_convout_bands, knob_wgrad_layer_wgs,
+        knob_skip_wgrad, knob_ablate_b, knob_ablate_f;
+    WgradKnobs wk;
+    // ---- settings for the forwards that follow (vae_set_recon_loss, vae_set_kl_objective); a forward snapshots them into its record ----
+    int recon = VAE_RECON_BCE, kl_kind = VAE_KL_PLAIN; double kl_param = 0.0;
+    // ---- the last forward ----
+    FwdRecord fwd;
+    // ---- diagnostics: phase stamps (vae_debug_stamps) and per-kernel timing (bench.py roofline: HIP events on the launch stream) ----
+    long long* dbg_buf = nullptr; char dbg_tag[32] = {0}; int dbg_epi = 0;
+    int prof = 0; const char* tag = nullptr; struct ProfRec { std::string name; hipEvent_t e0, e1; double bytes, flops; int side; int launches = 1; }; std::vector<ProfRec> prof_recs;
     hipStream_t cur_stream = nullptr; bool cur_stream_set = false;   // the caller's stream of the call in progress (profiling: tells critical-chain launches from side-stream ones)
 };
 
@@ -183,14 +177,39 @@ static inline size_t wgrad_slab_floats(const WgradKnobs& k, int B, int Hs, int W
     return per * nsplit;
 }
 
-// f16 storage: the gradient scale of a backward over B images (gmul / ginv above); 1 for the other storage types
+// f16 storage: the gradient scale of a backward over B images (FwdRecord::gmul / ginv); 1 for the other storage types
 static inline void set_grad_scale(vae_ctx* c, int B) {
     // dL/dlogit is O(1/(B*H*W)), far below the smallest f16 normal; 2^ceil(log2(B*H*W)) / 16 puts the stored dz around 2^-4, mid-range
-    c->gmul = 1.f; c->ginv = 1.f;
+    c->fwd.gmul = 1.f; c->fwd.ginv = 1.f;
     if (c->dtype == VAE_DTYPE_F16) {
         const int e = std::max(0, ilog2(B) + 2 * ilog2(c->H) - 4);
-        c->gmul = ldexpf(1.f, e); c->ginv = ldexpf(1.f, -e);
+        c->fwd.gmul = ldexpf(1.f, e); c->fwd.ginv = ldexpf(1.f, -e);
     }
+}
+
+// every entry point that launches on behalf of the context: the caller's stream of the call in progress (profiling)
+static inline void enter(vae_ctx* c, hipStream_t st) { c->cur_stream = st; c->cur_stream_set = true; }
+
+// The context holds no forward: nothing to score or differentiate until the next begin_forward.
+static inline void drop_forward(vae_ctx* c) {
+    FwdRecord& f = c->fwd;
+    f.kind = FwdRecord::NONE; f.B = 0; f.trained = 0;
+    f.kl_pending = 0; f.convout_pending = 0; f.dlogit_valid = 0; f.loss_out3 = nullptr; f.bwd_half_done = 0;
+}
+// A forward of `kind` over B images starts on `st`: the previous one is gone, the settings are snapshotted, and the statistics'
+// memset is the first thing enqueued on `st`.  The entry point then records the caller tensors this kind has (the rest stay null).
+static inline int begin_forward(vae_ctx* c, FwdRecord::Kind kind, int B, int train, hipStream_t st) {
+    enter(c, st);
+    drop_forward(c);
+    HIP_CHECK_RET(hipMemsetAsync(c->dstats, 0, c->n_dstats * sizeof(double), st));
+    FwdRecord& f = c->fwd;
+    f.kind = kind; f.B = B; f.trained = train; f.bwd_dirty = 0; f.recon = c->recon;
+    const bool elbo = kind == FwdRecord::FULL;   // (no ELBO follows an encoder-only or decoder-only pass)
+    f.kl_kind = elbo ? c->kl_kind : VAE_KL_PLAIN; f.kl_param = elbo ? c->kl_param : 0.0;
+    f.x = nullptr; f.xhat = f.mu = f.lv = f.z = nullptr;
+    if (kind != FwdRecord::DECODE) f.walk_dir = 1;   // (a pass through the encoder restarts the alternating tile walk)
+    set_grad_scale(c, B);
+    return 0;
 }
 
 // side streams (vae_api.hip)
@@ -202,6 +221,7 @@ int join_comm(vae_ctx* c, hipStream_t st);
 // wait a consumer's stream needs before it reads the factors / scalars (nothing when no reduction is outstanding)
 int launch_kl_shape(vae_ctx* c, hipStream_t st);
 int join_kl(vae_ctx* c, hipStream_t st);
+int launch_loss_finalize(vae_ctx* c, float* out3, float kld_weight, hipStream_t st);   // loss_finalize_kernel for the last forward (vae_api.hip)
 
 // entry points instantiated once per storage type (impl_bf16.hip, impl_f16.hip, impl_f32.hip)
 template <typename T> int pack_weights(vae_ctx* c, const float* params, hipStream_t st);

@@ -203,7 +203,7 @@ static int launch_conv_pipe(vae_ctx* c, ConvArgs<T> a, bool is_down, hipStream_t
     a.m_tx = fastdiv_magic(t.tiles_x); a.m_txy = fastdiv_magic(t.tiles_x * t.tiles_y);
     const int ntn = a.Cout / (32 * NT), n_pairs = n_mt * ntn;
     a.n_mt = n_mt; a.rev = ((c->knob_rev >> 2) & 1) ? ((a.epi == EPI_FWD) ? ((c->knob_rev >> 4) & 1) : 1) : 0;   // bit 2: backward launches, bit 4: forward too
-    if (c->knob_rev & 32) { a.rev = c->walk_dir; c->walk_dir ^= 1; }   // bit 5: alternate the direction launch by launch
+    if (c->knob_rev & 32) { a.rev = c->fwd.walk_dir; c->fwd.walk_dir ^= 1; }   // bit 5: alternate the direction launch by launch
     const size_t opitch = 32 * NT * sizeof(T) + 16;
     const size_t lds = ((3 * a.Cin * 4 + 15) & ~15) + (size_t)(wv ? 4 : 1) * TB * PHW * PATCH_PITCH + (lay24 ? 512 * (8 * NT * sizeof(T) + 16) : lay42 ? 256 * (16 * NT * sizeof(T) + 16) : lay22 ? 256 * (16 * NT * sizeof(T) + 16) : (is_down ? 128 : 256) * opitch) + 4 * NT * 32 * 2 * 4 +
                        std::max<size_t>((size_t)TB * PHW * 4, (lay24 || lay42) ? (size_t)5 * 512 : (size_t)(is_down ? 10 : 3) * (wv ? 64 : 256)) * 8;   // + the per-item staging table (padded to MAXI*SSTR)
@@ -247,7 +247,7 @@ static int launch_conv_pipe(vae_ctx* c, ConvArgs<T> a, bool is_down, hipStream_t
     return 0;
 }
 
-// (every caller reduces a parameter gradient: the result is written times c->ginv, the inverse of the f16 gradient scale)
+// (every caller reduces a parameter gradient: the result is written times c->fwd.ginv, the inverse of the f16 gradient scale)
 static int launch_reduce(const float* slab, int nslab, size_t n, float* out, int CA, int CB, hipStream_t st, vae_ctx* c) {
     ProfScope ps(c, "reduce_slab", 4.0 * n * (nslab + 1), 0, st);
     // many slabs of a small tensor (the output conv's 288 weights from 1536 workgroups): a handful of workgroups summing
@@ -261,11 +261,11 @@ static int launch_reduce(const float* slab, int nslab, size_t n, float* out, int
         if (ps.idx >= 0) c->prof_recs[ps.idx].launches = 2;   // (vae_profile_sequence lists one entry per device launch)
         hipLaunchKernelGGL(reduce_slab_kernel, dim3((unsigned)((n + 63) / 64), G), dim3(256), 0, st, slab, nslab, (int)n, tmp, 0, 0, 1.f, per);
         LAUNCH_CHECK("reduce_slab_kernel");
-        hipLaunchKernelGGL(reduce_slab_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, tmp, G, (int)n, out, CA, CB, c->ginv, G);
+        hipLaunchKernelGGL(reduce_slab_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, tmp, G, (int)n, out, CA, CB, c->fwd.ginv, G);
         LAUNCH_CHECK("reduce_slab_kernel");
         return 0;
     }
-    hipLaunchKernelGGL(reduce_slab_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, slab, nslab, (int)n, out, CA, CB, c->ginv, nslab);
+    hipLaunchKernelGGL(reduce_slab_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, slab, nslab, (int)n, out, CA, CB, c->fwd.ginv, nslab);
     LAUNCH_CHECK("reduce_slab_kernel");
     return 0;
 }
@@ -275,7 +275,7 @@ template <typename T>
 static int launch_wgrad(vae_ctx* c, WgradArgs<T> a, float* dw_out, hipStream_t st, float* slab_buf = nullptr, bool raw = false) {
     if (!slab_buf) slab_buf = c->slab;
     int nsplit, tps, WA, WB;
-    const bool big = (double)c->B * c->H * c->H >= (double)(1 << 21);   // e.g. 128x128 at batch >= 128
+    const bool big = (double)c->fwd.B * c->H * c->H >= (double)(1 << 21);   // e.g. 128x128 at batch >= 128
     // the prefetching variants index both operands with 32-bit BYTE offsets: tensors of 4 GiB or more (or the
     // knob_wgrad_force_simple diagnostic) take the synchronous kernel, which uses 64-bit element offsets
     const bool fits32 = 4.0 * a.B * a.Hs * a.Ws * std::max(a.CA, a.CB) * sizeof(T) < 4294967296.0 && !c->wk.force_simple;
@@ -284,9 +284,8 @@ static int launch_wgrad(vae_ctx* c, WgradArgs<T> a, float* dw_out, hipStream_t s
     // per-layer override of the wide-tile split (diagnostic: knob_wgrad_layer_wgs = layer_mask << 16 | workgroups;
     // bit i of the mask = BN layer i, named by the current tag)
     if (c->knob_wgrad_layer_wgs && c->tag) {
-        static const char* kTag[8] = {"encoder.0", "encoder.1", "encoder.2", "encoder.3", "decoder.0", "decoder.1", "decoder.2", "final_layer.0"};
         for (int i = 0; i < 8; ++i)
-            if (!strcmp(c->tag, kTag[i]) && ((c->knob_wgrad_layer_wgs >> (16 + i)) & 1)) wk.wide_wgs = wk.wgs = c->knob_wgrad_layer_wgs & 0xffff;
+            if (!strcmp(c->tag, kLayerTag[i]) && ((c->knob_wgrad_layer_wgs >> (16 + i)) & 1)) wk.wide_wgs = wk.wgs = c->knob_wgrad_layer_wgs & 0xffff;
     }
     const size_t need = wgrad_slab_floats(wk, a.B, a.Hs, a.Ws, a.CA, a.CB, &nsplit, &tps, &WA, &WB, pre, big);
     if (need > c->slab_floats) return vae_set_error("wgrad", "slab too small");
@@ -405,7 +404,7 @@ static BnFuse make_fuse_fwd(vae_ctx* c, int i, const float* params, float* bn_ru
     f.stat = l.stat_f; f.gamma = params + c->poff[l.p_gamma]; f.beta = params + c->poff[l.p_beta]; f.block = l.block;
     f.running_mean = bn_running ? bn_running + c->bnoff[i] : nullptr; f.running_var = bn_running ? bn_running + c->bnoff[i] + l.C : nullptr;
     f.nbt = nbt ? reinterpret_cast<long long*>(nbt) + i : nullptr;
-    f.C = l.C; f.count = (double)c->B * l.H * l.W; f.inv_count = 1.0 / f.count; f.eps = kBnEps; f.momentum = kBnMom; f.update_running = bn_running != nullptr;
+    f.C = l.C; f.count = (double)c->fwd.B * l.H * l.W; f.inv_count = 1.0 / f.count; f.eps = kBnEps; f.momentum = kBnMom; f.update_running = bn_running != nullptr;
     f.mode = BNF_FWD;
     return f;
 }
@@ -414,7 +413,7 @@ static BnFuse make_fuse_bwd(vae_ctx* c, int i, const float* params, float* grads
     BnFuse f; memset(&f, 0, sizeof(f));
     f.stat = l.stat_b; f.gamma = params + c->poff[l.p_gamma]; f.block = l.block;
     f.dgamma = grads + c->poff[l.p_gamma]; f.dbeta = grads + c->poff[l.p_beta]; f.dconv_bias = grads + c->poff[l.p_convb];
-    f.C = l.C; f.count = (double)c->B * l.H * l.W; f.inv_count = 1.0 / f.count; f.mode = BNF_BWD; f.ginv = c->ginv;
+    f.C = l.C; f.count = (double)c->fwd.B * l.H * l.W; f.inv_count = 1.0 / f.count; f.mode = BNF_BWD; f.ginv = c->fwd.ginv;
     return f;
 }
 static int bn_finalize_now(vae_ctx* c, const BnFuse& f, hipStream_t st) {
@@ -426,7 +425,7 @@ static int bn_finalize_now(vae_ctx* c, const BnFuse& f, hipStream_t st) {
 // Backward finalisation of a BN layer as its own launch; the consumers then read p0..p2 from the block (mode BNF_NONE).  After an
 // eval-mode forward always: BatchNorm on the running statistics (bn_eval_bwd_kernel, grad_paths.cuh).
 static int bn_bwd_standalone(vae_ctx* c, BnFuse& f, hipStream_t st) {
-    if (c->trained) { if (bn_finalize_now(c, f, st)) return -1; }
+    if (c->fwd.trained) { if (bn_finalize_now(c, f, st)) return -1; }
     else {
         ProfScope ps(c, "bn_eval_bwd_finalize", 0, 0, st);
         hipLaunchKernelGGL(bn_eval_bwd_kernel, dim3(1), dim3(256), 0, st, f);
@@ -461,7 +460,7 @@ template <typename T> static bool will_pipe(vae_ctx* c, const ConvArgs<T>& a) { 
 template <typename T>
 static int launch_convout_per_sample(vae_ctx* c, ConvOutArgs a, const BnFuse& f7, bool mfma_out, hipStream_t st) {
     const int B = a.B, H = a.H;
-    const bool mse = c->fwd_recon == VAE_RECON_MSE;
+    const bool mse = c->fwd.recon == VAE_RECON_MSE;
     a.part = c->ps_part; a.tB = c->ps_tb; a.xhat = nullptr; a.dlogit = nullptr; a.accum = nullptr;
     ProfScope ps(c, "convout_fwd_per_sample", ((double)sizeof(T) * 32 + 4.0) * B * H * H, 2.0 * 9 * 32 * B * H * H, st);
     if constexpr (sizeof(T) == 2) {
@@ -495,7 +494,6 @@ template <typename T>
 int decode_impl(vae_ctx* c, const float* z, int B, const float* params, float* bn_running, int64_t* nbt, int train,
                        const float* x, float* xhat, hipStream_t st) {
     const int H = c->H, L = c->L;
-    static const char* kLayerTag[8] = {"encoder.0", "encoder.1", "encoder.2", "encoder.3", "decoder.0", "decoder.1", "decoder.2", "final_layer.0"};
     c->tag = "latent";
     // decoder_input
     if (c->use_latent_mfma & 1) {   // 64 feature columns x the whole batch per workgroup on the exact-f32 MFMA (latent_mfma.cuh)
@@ -540,15 +538,15 @@ int decode_impl(vae_ctx* c, const float* z, int B, const float* params, float* b
         const bool mfma_out = sizeof(T) == 2 && c->use_mfma_convout && 64.0 * B * H * H < 4294967296.0;   // 32-bit byte offsets
         BnFuse f7;
         if (input_bn_fwd(c, 7, params, bn_running, nbt, train, mfma_out, &f7, st)) return -1;
-        c->convout_pending = 0; c->loss_out3 = nullptr; c->dlogit_valid = 1;
         if (train == 2 && mfma_out && c->use_fused_convout && c->use_fused_bn && !c->use_recomp_dz && f7.mode == BNF_FWD && H % 32 == 0) {
             // fused training step: forward AND backward of this layer run as one kernel at the start of the backward
-            c->pending_f7 = f7; c->convout_pending = 1; c->dlogit_valid = 0;
+            c->fwd.pending_f7 = f7; c->fwd.convout_pending = 1;
             return 0;
         }
+        c->fwd.dlogit_valid = 1;   // (begin_forward cleared both flags)
         if (c->ps_part) return launch_convout_per_sample<T>(c, a, f7, mfma_out, st);
         ProfScope ps(c, "convout_fwd+bce", ((double)sizeof(T) * 32 + 12.0) * B * H * H, 2.0 * 9 * 32 * B * H * H, st);
-        const bool mse = c->fwd_recon == VAE_RECON_MSE;
+        const bool mse = c->fwd.recon == VAE_RECON_MSE;
         bool launched = false;
         if constexpr (sizeof(T) == 2) {
             if (mfma_out) {
@@ -577,10 +575,6 @@ template <typename T>
 int encode_impl(vae_ctx* c, const float* x, int B, const float* params, float* bn_running, int64_t* nbt,
                 const float* eps, uint64_t seed, int train, float* mu, float* lv, float* z, hipStream_t st) {
     const int H = c->H, L = c->L;
-    c->B = B; c->trained = train; c->x = x; c->mu = mu; c->lv = lv; c->z = z;
-    set_grad_scale(c, B);   // f16 storage: gradient scale for the backward of this forward (vae_ctx.h)
-    HIP_CHECK_RET(hipMemsetAsync(c->dstats, 0, c->n_dstats * sizeof(double), st)); c->bwd_dirty = 0; c->walk_dir = 1;
-    static const char* kLayerTag[8] = {"encoder.0", "encoder.1", "encoder.2", "encoder.3", "decoder.0", "decoder.1", "decoder.2", "final_layer.0"};
     // encoder block 0 (reads the raw f32 weights); the MFMA layers' packed weight images are built meanwhile
     c->tag = kLayerTag[0];
     {
@@ -643,11 +637,10 @@ int encode_impl(vae_ctx* c, const float* x, int B, const float* params, float* b
 template <typename T>
 int forward_impl(vae_ctx* c, const float* x, int B, const float* params, float* bn_running, int64_t* nbt,
                         const float* eps, uint64_t seed, int train, float* xhat, float* mu, float* lv, float* z, hipStream_t st) {
-    c->xhat = xhat; c->fwd_kind = 0;
     const int rc = encode_impl<T>(c, x, B, params, bn_running, nbt, eps, seed, train, mu, lv, z, st);
     if (rc) return rc;
     // free bits / capacity target: the batch reduction its loss and backward need, beside the decoder (nothing for the plain objective)
-    if (c->fwd_kl_kind != VAE_KL_PLAIN && launch_kl_shape(c, st)) return -1;
+    if (c->fwd.kl_kind != VAE_KL_PLAIN && launch_kl_shape(c, st)) return -1;
     return decode_impl<T>(c, z, B, params, bn_running, nbt, train, x, xhat, st);
 }
 
@@ -661,8 +654,8 @@ static bool convt_fused_ok(vae_ctx* c, int i) {
     const BnLayer& l = c->lay[i]; const BnLayer& lp = c->lay[i - 1];
     const int Hs = l.H / 2, Ws = l.W / 2, CLO = lp.C;
     if (!(c->use_fused_wgrad & 1) || !c->use_pipelined || l.C != 32 || (CLO != 32 && CLO != 64) || Hs % 8 || Ws % 16) return false;
-    if (4.0 * c->B * Hs * Ws * 32 * sizeof(T) >= 4294967296.0 || 1.0 * c->B * Hs * Ws * CLO * sizeof(T) >= 4294967296.0) return false;   // 32-bit byte offsets
-    const int grid = std::min(c->B * (Ws / 16) * (Hs / 8), c->knob_fused_grid);
+    if (4.0 * c->fwd.B * Hs * Ws * 32 * sizeof(T) >= 4294967296.0 || 1.0 * c->fwd.B * Hs * Ws * CLO * sizeof(T) >= 4294967296.0) return false;   // 32-bit byte offsets
+    const int grid = std::min(c->fwd.B * (Ws / 16) * (Hs / 8), c->knob_fused_grid);
     return (size_t)grid * 9 * CLO * 32 <= c->fused_slab_floats;
 }
 // recomp (layer 7 only): dz of the layer was not stored by the output-conv backward; it is recomputed from dl_src * dl_scale
@@ -678,17 +671,17 @@ static int launch_convt_fused(vae_ctx* c, int i, const float* params, float* gra
         ConvTFusedArgs<T> a; memset(&a, 0, sizeof(a));
         a.dz = reinterpret_cast<const T*>(l.dz); a.y = reinterpret_cast<const T*>(l.y); a.gcoef = l.block + LC_P0 * l.C;
         a.fuse = make_fuse_bwd(c, i, params, grads);
-        if (!c->use_fused_bn || !c->trained) { if (bn_bwd_standalone(c, a.fuse, st)) return -1; }   // standalone finalisation: coefficients from the block
+        if (!c->use_fused_bn || !c->fwd.trained) { if (bn_bwd_standalone(c, a.fuse, st)) return -1; }   // standalone finalisation: coefficients from the block
         a.wp = reinterpret_cast<const T*>(c->wp_dg[i]);
         a.yprev = reinterpret_cast<const T*>(lp.y); a.ocoef = lp.block; a.dzprev = reinterpret_cast<T*>(lp.dz); a.stat = lp.stat_b;
         a.slab = c->fused_slab[fs]; a.slope = kSlope;
-        a.B = c->B; a.Hs = Hs; a.Ws = Ws; a.tiles_x = Ws / 16; a.tiles_y = Hs / 8; a.n_tiles = c->B * a.tiles_x * a.tiles_y;
+        a.B = c->fwd.B; a.Hs = Hs; a.Ws = Ws; a.tiles_x = Ws / 16; a.tiles_y = Hs / 8; a.n_tiles = c->fwd.B * a.tiles_x * a.tiles_y;
         a.rev = (c->knob_rev >> 2) & 1;
-        a.dlogit = dl_src; a.gscale = dl_scale; a.gmul = c->gmul; a.wout = c->wout_t; a.fcoef = l.block;
+        a.dlogit = dl_src; a.gscale = dl_scale; a.gmul = c->fwd.gmul; a.wout = c->wout_t; a.fcoef = l.block;
         if (recomp && (CLO != 32 || !dl_src)) return vae_set_error("convt_fused", "recomputed dz: final_layer.0 only");
         const int grid = std::min(a.n_tiles, c->knob_fused_grid);
         const size_t lds = convt_fused_lds(CLO, recomp);
-        const double px = (double)c->B * Hs * Ws;
+        const double px = (double)c->fwd.B * Hs * Ws;
         {
             ProfScope ps(c, recomp ? "convT_bwd_fused(dz recomputed+dgrad+wgrad)" : "convT_bwd_fused(dgrad+wgrad)",
                          sizeof(T) * ((recomp ? 1.0 : 2.0) * 4 * px * 32 + 2.0 * px * CLO + 9.0 * 32 * CLO) + 4.0 * 9 * 32 * CLO + (recomp ? 4.0 * 4 * px : 0.0),
@@ -715,19 +708,19 @@ static int launch_conv_fused(vae_ctx* c, int i, const float* params, float* grad
         const BnLayer& l = c->lay[i]; const BnLayer& lp = c->lay[i - 1];
         const int Hs = l.H, Ws = l.W;
         if (!(c->use_fused_wgrad & 2) || !c->use_pipelined || l.C != 64 || lp.C != 32 || Hs % 8 || Ws % 8) return 1;
-        if (4.0 * c->B * Hs * Ws * 32 * sizeof(T) >= 4294967296.0 || 1.0 * c->B * Hs * Ws * 64 * sizeof(T) >= 4294967296.0) return 1;   // 32-bit byte offsets
+        if (4.0 * c->fwd.B * Hs * Ws * 32 * sizeof(T) >= 4294967296.0 || 1.0 * c->fwd.B * Hs * Ws * 64 * sizeof(T) >= 4294967296.0) return 1;   // 32-bit byte offsets
         ConvFusedArgs<T> a; memset(&a, 0, sizeof(a));
-        a.tiles_x = Ws / 8; a.tiles_y = Hs / 8; a.n_tiles = c->B * a.tiles_x * a.tiles_y;
+        a.tiles_x = Ws / 8; a.tiles_y = Hs / 8; a.n_tiles = c->fwd.B * a.tiles_x * a.tiles_y;
         const int grid = std::min(a.n_tiles, c->knob_fused_grid);
         if ((size_t)grid * 9 * 64 * 32 > c->fused_slab_floats) return 1;
         a.dz = reinterpret_cast<const T*>(l.dz); a.y = reinterpret_cast<const T*>(l.y); a.gcoef = l.block + LC_P0 * l.C;
         a.fuse = make_fuse_bwd(c, i, params, grads);
-        if (!c->use_fused_bn || !c->trained) { if (bn_bwd_standalone(c, a.fuse, st)) return -1; }
+        if (!c->use_fused_bn || !c->fwd.trained) { if (bn_bwd_standalone(c, a.fuse, st)) return -1; }
         a.wp = reinterpret_cast<const T*>(c->wp_dg[i]);
         a.yprev = reinterpret_cast<const T*>(lp.y); a.ocoef = lp.block; a.dzprev = reinterpret_cast<T*>(lp.dz); a.stat = lp.stat_b;
-        a.slab = c->fused_slab[2]; a.slope = kSlope; a.B = c->B; a.Hs = Hs; a.Ws = Ws; a.rev = (c->knob_rev >> 2) & 1; a.ablate = c->knob_ablate_f;
+        a.slab = c->fused_slab[2]; a.slope = kSlope; a.B = c->fwd.B; a.Hs = Hs; a.Ws = Ws; a.rev = (c->knob_rev >> 2) & 1; a.ablate = c->knob_ablate_f;
         const size_t lds = conv_fused_lds();
-        const double px = (double)c->B * Hs * Ws;
+        const double px = (double)c->fwd.B * Hs * Ws;
         {
             ProfScope ps(c, "conv_bwd_fused(dgrad+wgrad)", sizeof(T) * (2.0 * px * 64 + 2.0 * 4 * px * 32 + 9.0 * 32 * 64) + 4.0 * 9 * 32 * 64,
                          2.0 * 2 * 9 * 32 * 64 * px, st);
@@ -757,11 +750,11 @@ static bool raw_wgrad_ok(vae_ctx* c, int i) {
 static int bwd_clear_stats(vae_ctx* c, hipStream_t st) {
     size_t nfwd = 0;
     for (int i = 0; i < 8; ++i) nfwd += 2 * kBnC[i] * STAT_R;
-    if (c->bwd_dirty) {   // (the forward zeroed every accumulator; only a repeated backward has to clear its own)
+    if (c->fwd.bwd_dirty) {   // (the forward zeroed every accumulator; only a repeated backward has to clear its own)
         HIP_CHECK_RET(hipMemsetAsync(c->dstats + nfwd, 0, nfwd * sizeof(double), st));   // stat_b
         for (int rep = 0; rep < STAT_R; ++rep) HIP_CHECK_RET(hipMemsetAsync(c->accum + rep * 8 + 2, 0, sizeof(double), st));
     }
-    c->bwd_dirty = 1;
+    c->fwd.bwd_dirty = 1;
     return 0;
 }
 
@@ -770,22 +763,21 @@ template <typename T>
 static int backward_first(vae_ctx* c, const float* x, const float* params, float* grads, const float* g_xhat, const float* gscale,
                          const float* g_mu, const float* g_lv, const float* g_z, const float* g_pre, float kld_weight, int add_kl,
                          hipStream_t st, bool ex = false) {
-    if (!c->B || !(c->trained || ex)) return vae_set_error("vae_backward", "no train-mode forward to differentiate");
-    const int B = c->B, H = c->H, L = c->L;
+    if (!c->fwd || !(c->fwd.trained || ex)) return vae_set_error("vae_backward", "no train-mode forward to differentiate");
+    const int B = c->fwd.B, H = c->H, L = c->L;
     if (bwd_clear_stats(c, st)) return -1;
     const float* dl_src = c->dlogit; const float* dl_scale = gscale;
-    const bool step7 = c->convout_pending != 0;
+    const bool step7 = c->fwd.convout_pending != 0;
     if (step7 && (g_xhat || gscale || !add_kl)) return vae_set_error("vae_backward", "the forward ran with train = 2: only the standard ELBO backward (no upstream gradient on xhat, no loss scale) can follow");
-    if (!step7 && add_kl && !c->dlogit_valid) return vae_set_error("vae_backward", "this forward's output-conv gradient was already consumed (train = 2 forwards can be differentiated once)");
+    if (!step7 && add_kl && !c->fwd.dlogit_valid) return vae_set_error("vae_backward", "this forward's output-conv gradient was already consumed (train = 2 forwards can be differentiated once)");
     if (g_xhat || !add_kl) {
         // explicit upstream gradient on xhat (plus, when add_kl, the fused standard-ELBO term)
         const long n = (long)B * H * H;
         hipLaunchKernelGGL(dlogit_combine_kernel, dim3((unsigned)std::min<long>((n + 255) / 256, 4096)), dim3(256), 0, st,
-                           g_xhat, c->xhat, add_kl ? c->dlogit : nullptr, gscale, c->dlogit2, n);
+                           g_xhat, c->fwd.xhat, add_kl ? c->dlogit : nullptr, gscale, c->dlogit2, n);
         LAUNCH_CHECK("dlogit_combine_kernel");
         dl_src = c->dlogit2; dl_scale = nullptr;
     }
-    static const char* kLayerTag[8] = {"encoder.0", "encoder.1", "encoder.2", "encoder.3", "decoder.0", "decoder.1", "decoder.2", "final_layer.0"};
     // output conv backward + final_layer BN/LeakyReLU prologue
     c->tag = "final_layer.3";
     int cgrid = 0;
@@ -794,7 +786,7 @@ static int backward_first(vae_ctx* c, const float* x, const float* params, float
         ConvOutBwdArgs a;
         a.yf = c->lay[7].y; a.ocoef = c->lay[7].block; a.wt = c->wout_t; a.dlogit = dl_src; a.gscale = dl_scale;
         a.dz = c->lay[7].dz; a.slab = c->use_side_stream ? c->side_slab[0] : c->slab; a.stat = c->lay[7].stat_b; a.dbias = c->accum + 2; a.B = B; a.H = H; a.W = H; a.slope = kSlope;
-        a.gmul = c->gmul;   // the gradient scale enters the backward here (and in latent_bwd / fc_dgrad for the other upstream gradients)
+        a.gmul = c->fwd.gmul;   // the gradient scale enters the backward here (and in latent_bwd / fc_dgrad for the other upstream gradients)
         const long P = (long)B * H * H;
         int grid = (int)std::min<long>((P + 63) / 64, 1024);
         const bool will_recomp = sizeof(T) == 2 && c->use_mfma_convout && c->use_recomp_dz && convt_fused_ok<T>(c, 7);
@@ -805,10 +797,10 @@ static int backward_first(vae_ctx* c, const float* x, const float* params, float
             if (step7 && c->use_convout_stream && H == cos::RW) {
                 // row-streaming form: units = (image, band of RB rows); bands only where whole images would leave CUs idle or the
                 // last round mostly empty (a band costs RB/2 + 3 ticks and restages 4 rows)
-                ConvOutStreamArgs<T> m; m.fuse = c->pending_f7;
-                m.yf = reinterpret_cast<const T*>(c->lay[7].y); m.wt = c->wout_t; m.bias = params + c->poff[39]; m.target = c->x;
-                m.xhat = c->xhat; m.accum = c->accum; m.dz = reinterpret_cast<T*>(c->lay[7].dz); m.slab = a.slab; m.stat = a.stat;
-                m.B = B; m.H = H; m.inv_n = (float)(1.0 / ((double)B * H * H)); m.slope = kSlope; m.gmul = c->gmul;
+                ConvOutStreamArgs<T> m; m.fuse = c->fwd.pending_f7;
+                m.yf = reinterpret_cast<const T*>(c->lay[7].y); m.wt = c->wout_t; m.bias = params + c->poff[39]; m.target = c->fwd.x;
+                m.xhat = c->fwd.xhat; m.accum = c->accum; m.dz = reinterpret_cast<T*>(c->lay[7].dz); m.slab = a.slab; m.stat = a.stat;
+                m.B = B; m.H = H; m.inv_n = (float)(1.0 / ((double)B * H * H)); m.slope = kSlope; m.gmul = c->fwd.gmul;
                 m.dbg = (c->dbg_buf && !strcmp(c->dbg_tag, "final_layer.3")) ? c->dbg_buf : nullptr;
                 const int ncu = 256;
                 long best = -1; int nb = 1;
@@ -820,7 +812,7 @@ static int backward_first(vae_ctx* c, const float* x, const float* params, float
                 m.nb = nb; m.RB = H / nb; m.n_units = B * nb;
                 grid = std::min(m.n_units, ncu);
                 const size_t lds = convout_stream_lds();
-                if (c->fwd_recon == VAE_RECON_MSE) {
+                if (c->fwd.recon == VAE_RECON_MSE) {
                     if (set_lds(convout_stream_kernel<T, VAE_RECON_MSE>, lds)) return -1;
                     hipLaunchKernelGGL((convout_stream_kernel<T, VAE_RECON_MSE>), dim3(grid), dim3(1024), lds, st, m);
                 } else {
@@ -828,17 +820,17 @@ static int backward_first(vae_ctx* c, const float* x, const float* params, float
                     hipLaunchKernelGGL((convout_stream_kernel<T, VAE_RECON_BCE>), dim3(grid), dim3(1024), lds, st, m);
                 }
                 launched = true;
-                c->convout_pending = 0;
+                c->fwd.convout_pending = 0;
             }
             if (step7 && !launched) {
-                ConvOutStepArgs<T> m; m.fuse = c->pending_f7; m.rev = (c->knob_rev >> 1) & 1;
-                m.yf = reinterpret_cast<const T*>(c->lay[7].y); m.wt = c->wout_t; m.bias = params + c->poff[39]; m.target = c->x;
-                m.xhat = c->xhat; m.accum = c->accum; m.dz = reinterpret_cast<T*>(c->lay[7].dz); m.slab = a.slab; m.stat = a.stat;
+                ConvOutStepArgs<T> m; m.fuse = c->fwd.pending_f7; m.rev = (c->knob_rev >> 1) & 1;
+                m.yf = reinterpret_cast<const T*>(c->lay[7].y); m.wt = c->wout_t; m.bias = params + c->poff[39]; m.target = c->fwd.x;
+                m.xhat = c->fwd.xhat; m.accum = c->accum; m.dz = reinterpret_cast<T*>(c->lay[7].dz); m.slab = a.slab; m.stat = a.stat;
                 m.B = B; m.H = H; m.W = H; m.n_tiles = B * (H / 8) * (H / 32);
-                m.inv_n = (float)(1.0 / ((double)B * H * H)); m.slope = kSlope; m.gmul = c->gmul; m.ablate = c->knob_ablate_f;
+                m.inv_n = (float)(1.0 / ((double)B * H * H)); m.slope = kSlope; m.gmul = c->fwd.gmul; m.ablate = c->knob_ablate_f;
                 grid = std::min(m.n_tiles, c->knob_convout_step_grid);   // 512 resident (2 per CU by LDS): two full rounds
                 const size_t lds = convout_step_lds();
-                if (c->fwd_recon == VAE_RECON_MSE) {
+                if (c->fwd.recon == VAE_RECON_MSE) {
                     if (set_lds(convout_step_mfma_kernel<T, VAE_RECON_MSE>, lds)) return -1;
                     hipLaunchKernelGGL((convout_step_mfma_kernel<T, VAE_RECON_MSE>), dim3(grid), dim3(256), lds, st, m);
                 } else {
@@ -846,7 +838,7 @@ static int backward_first(vae_ctx* c, const float* x, const float* params, float
                     hipLaunchKernelGGL((convout_step_mfma_kernel<T, VAE_RECON_BCE>), dim3(grid), dim3(256), lds, st, m);
                 }
                 launched = true;
-                c->convout_pending = 0;
+                c->fwd.convout_pending = 0;
             }
         }
         if constexpr (sizeof(T) == 2) {
@@ -871,14 +863,12 @@ static int backward_first(vae_ctx* c, const float* x, const float* params, float
         SideFork f = fork_side(c, st, 0);   // the kernel above wrote its partial sums into side stream 0's slab
         if (f.rc) return f.rc;
         if (launch_reduce(f.slab, cgrid, 288, grads + c->poff[38], 1, 32, f.st, c)) return -1;
-        hipLaunchKernelGGL(accum_to_f32_kernel, dim3(1), dim3(64), 0, f.st, c->accum + 2, grads + c->poff[39], c->ginv);
+        hipLaunchKernelGGL(accum_to_f32_kernel, dim3(1), dim3(64), 0, f.st, c->accum + 2, grads + c->poff[39], c->fwd.ginv);
         LAUNCH_CHECK("accum_to_f32_kernel");
-        if (step7 && c->loss_out3) {   // the ELBO scalars vae_loss_deferred asked for: the BCE sum exists only now
+        if (step7 && c->fwd.loss_out3) {   // the ELBO scalars vae_loss_deferred asked for: the BCE sum exists only now
             if (c->kl_shaped() && join_kl(c, f.st)) return -1;
-            hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, f.st, c->accum, c->loss_out3,
-                               1.0 / ((double)B * H * H), 1.0 / (double)B, c->loss_kw, STAT_R, c->kl_shaped());
-            LAUNCH_CHECK("loss_finalize_kernel");
-            c->loss_out3 = nullptr;
+            if (launch_loss_finalize(c, c->fwd.loss_out3, c->fwd.loss_kw, f.st)) return -1;
+            c->fwd.loss_out3 = nullptr;
         }
     }
     // decoder stack: ConvTranspose2d layers 7 (final_layer.0), 6, 5, 4
@@ -909,7 +899,7 @@ static int backward_first(vae_ctx* c, const float* x, const float* params, float
         }
         // BatchNorm backward of this layer: folded into both consumers (the input-gradient kernel records it)
         BnFuse fb = make_fuse_bwd(c, i, params, grads);
-        if (!(c->use_fused_bn && will_pipe(c, a)) || !c->trained) { if (bn_bwd_standalone(c, fb, st)) return -1; }
+        if (!(c->use_fused_bn && will_pipe(c, a)) || !c->fwd.trained) { if (bn_bwd_standalone(c, fb, st)) return -1; }
         w.fuse = fb; a.fuse = fb;
         // deep layers: the input-gradient kernel materialises g = BN-backward(dz, y) while staging it; the weight gradient then
         // reads g and the forward's materialised activation as plain copies (it must follow the input-gradient launch)
@@ -936,8 +926,7 @@ template <typename T>
 static int backward_second(vae_ctx* c, const float* x, const float* params, float* grads, const float* gscale,
                            const float* g_mu, const float* g_lv, const float* g_z, const float* g_pre, float kld_weight, int add_kl,
                            hipStream_t st, int mode = 0, float* out = nullptr) {
-    const int B = c->B, H = c->H, L = c->L;
-    static const char* kLayerTag[8] = {"encoder.0", "encoder.1", "encoder.2", "encoder.3", "decoder.0", "decoder.1", "decoder.2", "final_layer.0"};
+    const int B = c->fwd.B, H = c->H, L = c->L;
     // decoder_input backward, reparameterisation + KL backward
     c->tag = "latent";
     {
@@ -947,8 +936,8 @@ static int backward_second(vae_ctx* c, const float* x, const float* params, floa
             SideFork f = fork_side(c, st);
             if (f.rc) return f.rc;
             BatchGemmArgs g; memset(&g, 0, sizeof(g));
-            g.X = c->dd0; g.coef = nullptr; g.slope = 1.f; g.Y = c->z; g.ldy = L; g.ncols = L; g.ones_col = 1;
-            g.out0 = grads + c->poff[20]; g.outb = grads + c->poff[21]; g.B = B; g.F = (int)c->F; g.L = L; g.s2 = c->s2; g.scale = c->ginv;
+            g.X = c->dd0; g.coef = nullptr; g.slope = 1.f; g.Y = c->fwd.z; g.ldy = L; g.ncols = L; g.ones_col = 1;
+            g.out0 = grads + c->poff[20]; g.outb = grads + c->poff[21]; g.B = B; g.F = (int)c->F; g.L = L; g.s2 = c->s2; g.scale = c->fwd.ginv;
             ProfScope ps(c, "decin_wgrad", (double)sizeof(T) * B * (double)c->F + 4.0 * c->F * L, 2.0 * B * c->F * L, f.st);
             const size_t lds = batch_gemm_lds();
             if (set_lds(batch_gemm_kernel<T, false>, lds)) return -1;
@@ -963,7 +952,7 @@ static int backward_second(vae_ctx* c, const float* x, const float* params, floa
             dim3 grid((unsigned)(c->F / 256), (L + 31) / 32, nz);
             {
                 ProfScope ps(c, "decin_wgrad", (double)sizeof(T) * B * (double)c->F + 4.0 * c->F * L, 2.0 * B * c->F * L, f.st);
-                hipLaunchKernelGGL((decin_wgrad_kernel<T>), grid, dim3(256), 0, f.st, reinterpret_cast<const T*>(c->dd0), c->z, sw, sb, B, (int)c->F, L, c->s2, bsplit);
+                hipLaunchKernelGGL((decin_wgrad_kernel<T>), grid, dim3(256), 0, f.st, reinterpret_cast<const T*>(c->dd0), c->fwd.z, sw, sb, B, (int)c->F, L, c->s2, bsplit);
                 LAUNCH_CHECK("decin_wgrad_kernel");
             }
             if (launch_reduce(sw, nz, (size_t)c->F * L, grads + c->poff[20], 0, 0, f.st, c)) return -1;
@@ -979,15 +968,15 @@ static int backward_second(vae_ctx* c, const float* x, const float* params, floa
         if (mode == 2) {
             if (!out) return join_sides(c, st);
             ProfScope ps(c, "latent_dz", 4.0 * nsplit * B * L + 4.0 * B * L, 0, st);
-            hipLaunchKernelGGL(latent_dz_kernel, dim3((B * L + 255) / 256), dim3(256), 0, st, c->slab, nsplit, c->npad_di, B, L, c->ginv, out);
+            hipLaunchKernelGGL(latent_dz_kernel, dim3((B * L + 255) / 256), dim3(256), 0, st, c->slab, nsplit, c->npad_di, B, L, c->fwd.ginv, out);
             LAUNCH_CHECK("latent_dz_kernel");
             return join_sides(c, st);
         }
         LatentBwdArgs lb;
-        lb.slab = c->slab; lb.nslab = nsplit; lb.npad = c->npad_di; lb.mu = c->mu; lb.lv = c->lv; lb.eps = c->eps; lb.gscale = gscale;
-        lb.gmu = g_mu; lb.glv = g_lv; lb.gz = g_z; lb.dlat = c->dlat; lb.B = B; lb.L = L; lb.kld_weight = kld_weight; lb.add_kl = add_kl; lb.gmul = c->gmul;
+        lb.slab = c->slab; lb.nslab = nsplit; lb.npad = c->npad_di; lb.mu = c->fwd.mu; lb.lv = c->fwd.lv; lb.eps = c->eps; lb.gscale = gscale;
+        lb.gmu = g_mu; lb.glv = g_lv; lb.gz = g_z; lb.dlat = c->dlat; lb.B = B; lb.L = L; lb.kld_weight = kld_weight; lb.add_kl = add_kl; lb.gmul = c->fwd.gmul;
         lb.factor = nullptr;
-        if (add_kl && c->fwd_kl_kind != VAE_KL_PLAIN) {   // the objective the forward recorded: its per-dimension factors
+        if (add_kl && c->fwd.kl_kind != VAE_KL_PLAIN) {   // the objective the forward recorded: its per-dimension factors
             if (join_kl(c, st)) return -1;
             lb.factor = c->kl_factor();
             hipLaunchKernelGGL(latent_bwd_kernel<true>, dim3((B * L * LAT_LANES + 255) / 256), dim3(256), 0, st, lb);
@@ -996,7 +985,7 @@ static int backward_second(vae_ctx* c, const float* x, const float* params, floa
         if (!lat_mfma) {
             SideFork f = fork_side(c, st);
             if (f.rc) return f.rc;
-            hipLaunchKernelGGL(colsum_kernel, dim3(2 * L), dim3(64), 0, f.st, c->dlat, B, 2 * L, grads + c->poff[17], grads + c->poff[19], L, c->ginv);
+            hipLaunchKernelGGL(colsum_kernel, dim3(2 * L), dim3(64), 0, f.st, c->dlat, B, 2 * L, grads + c->poff[17], grads + c->poff[19], L, c->fwd.ginv);
             LAUNCH_CHECK("colsum_kernel");
         }
     }
@@ -1008,7 +997,7 @@ static int backward_second(vae_ctx* c, const float* x, const float* params, floa
         BatchGemmArgs g; memset(&g, 0, sizeof(g));
         g.X = c->lay[3].y; g.coef = c->lay[3].block; g.slope = kSlope; g.Y = c->dlat; g.ldy = 2 * L; g.ncols = 2 * L; g.ones_col = 0;
         g.out0 = grads + c->poff[16]; g.out1 = grads + c->poff[18]; g.colsum0 = grads + c->poff[17]; g.colsum1 = grads + c->poff[19];
-        g.B = B; g.F = (int)c->F; g.L = L; g.s2 = c->s2; g.scale = c->ginv;
+        g.B = B; g.F = (int)c->F; g.L = L; g.s2 = c->s2; g.scale = c->fwd.ginv;
         ProfScope ps(c, "fc_wgrad", (double)sizeof(T) * B * (double)c->F + 8.0 * c->F * L, 4.0 * B * c->F * L, f.st);
         const size_t lds = batch_gemm_lds();
         if (set_lds(batch_gemm_kernel<T, true>, lds)) return -1;
@@ -1035,7 +1024,7 @@ static int backward_second(vae_ctx* c, const float* x, const float* params, floa
     if ((c->use_latent_mfma & 8) && 2 * L <= 256) {
         RowGemmArgs g; memset(&g, 0, sizeof(g));
         g.Y = c->dlat; g.ldy = 2 * L; g.K = 2 * L; g.Wp = c->fcpack; g.npad = c->npad_fc; g.out = c->lay[3].dz;
-        g.y = c->lay[3].y; g.ocoef = c->lay[3].block; g.slope = kSlope; g.gpre = g_pre; g.gmul = c->gmul; g.stat = c->lay[3].stat_b;
+        g.y = c->lay[3].y; g.ocoef = c->lay[3].block; g.slope = kSlope; g.gpre = g_pre; g.gmul = c->fwd.gmul; g.stat = c->lay[3].stat_b;
         g.B = B; g.F = (int)c->F; g.s2 = c->s2;
         ProfScope ps2(c, "fc_dgrad", (double)sizeof(T) * (2.0 * B * c->F + 2.0 * c->F * L), 4.0 * B * c->F * L, st);
         const size_t lds = row_gemm_lds<T>();
@@ -1046,7 +1035,7 @@ static int backward_second(vae_ctx* c, const float* x, const float* params, floa
         FcDgradArgs<T> d;
         d.dlat = c->dlat; d.wp = reinterpret_cast<const T*>(c->fcpack); d.npad = c->npad_fc; d.y = reinterpret_cast<const T*>(c->lay[3].y);
         d.ocoef = c->lay[3].block; d.slope = kSlope; d.gpre = g_pre; d.dz = reinterpret_cast<T*>(c->lay[3].dz); d.stat = c->lay[3].stat_b;
-        d.B = B; d.F = (int)c->F; d.L2 = 2 * L; d.s2 = c->s2; d.gmul = c->gmul;
+        d.B = B; d.F = (int)c->F; d.L2 = 2 * L; d.s2 = c->s2; d.gmul = c->fwd.gmul;
         ProfScope ps2(c, "fc_dgrad", (double)sizeof(T) * (2.0 * B * c->F + 2.0 * c->F * L), 4.0 * B * c->F * L, st);
         d.bt_per_wg = std::max(16, ((B + 7) / 8 + 15) / 16 * 16);   // <= 8 workgroups per channel: fewer same-address atomics
         bool wide = false;
@@ -1092,7 +1081,7 @@ static int backward_second(vae_ctx* c, const float* x, const float* params, floa
         a.out = reinterpret_cast<T*>(lp.dz); a.yout = reinterpret_cast<const T*>(lp.y); a.ocoef = lp.block; a.oslope = kSlope; a.stat = lp.stat_b; a.epi = EPI_BWD;
         a.B = B; a.Hs = l.H; a.Ws = l.W; a.Cin = l.C; a.Cout = lp.C;
         BnFuse fb = make_fuse_bwd(c, i, params, grads);
-        if (!(c->use_fused_bn && will_pipe(c, a)) || !c->trained) { if (bn_bwd_standalone(c, fb, st)) return -1; }
+        if (!(c->use_fused_bn && will_pipe(c, a)) || !c->fwd.trained) { if (bn_bwd_standalone(c, fb, st)) return -1; }
         w.fuse = fb; a.fuse = fb;
         const bool raw = raw_wgrad_ok<T>(c, i) && l.dy && will_pipe(c, a) && lp.act_ok;
         if (raw) {   // (as in the decoder loop)
@@ -1109,7 +1098,7 @@ static int backward_second(vae_ctx* c, const float* x, const float* params, floa
     {
         c->tag = kLayerTag[0];
         BnFuse fb0 = make_fuse_bwd(c, 0, params, grads);
-        if (!c->use_fused_bn || !(c->knob_lean & 2) || !c->trained) { if (bn_bwd_standalone(c, fb0, st)) return -1; }
+        if (!c->use_fused_bn || !(c->knob_lean & 2) || !c->fwd.trained) { if (bn_bwd_standalone(c, fb0, st)) return -1; }
         const long P = (long)B * (H / 2) * (H / 2);
         const int grid = (int)std::min<long>((P / 4 + 63) / 64, 512);   // (a thread takes quads of 4 output pixels)
         // last link of the chain: stays on the caller's stream (a side stream would only add an event round trip)
@@ -1126,7 +1115,7 @@ static int backward_second(vae_ctx* c, const float* x, const float* params, floa
             const long Q = (P + 63) / 64;
             ProfScope ps(c, "conv1_dgrad", (double)sizeof(T) * 64.0 * P + 4.0 * B * H * H, 2.0 * 9 * 32 * P, st);
             hipLaunchKernelGGL((conv1_dgrad_kernel<T>), dim3((unsigned)std::min<long>(Q, 2048)), dim3(256), 0, st, reinterpret_cast<const T*>(c->lay[0].dz),
-                               reinterpret_cast<const T*>(c->lay[0].y), c->lay[0].block + LC_P0 * 32, params + c->poff[0], out, B, H, H, c->ginv);
+                               reinterpret_cast<const T*>(c->lay[0].y), c->lay[0].block + LC_P0 * 32, params + c->poff[0], out, B, H, H, c->fwd.ginv);
             LAUNCH_CHECK("conv1_dgrad_kernel");
         }
     }
@@ -1140,24 +1129,24 @@ int backward_impl(vae_ctx* c, const float* x, const float* params, float* grads,
                          const float* g_mu, const float* g_lv, const float* g_z, const float* g_pre, float kld_weight, int add_kl,
                          int part, hipStream_t st) {
     if (part < 0 || part > 2) return vae_set_error("vae_backward", "part must be 0, 1 or 2");
-    if (c->fwd_kind != 0 && c->B) return vae_set_error("vae_backward", "the last forward ran the encoder or the decoder only: use vae_backward_ex");
+    if (c->fwd.kind == FwdRecord::ENCODE || c->fwd.kind == FwdRecord::DECODE) return vae_set_error("vae_backward", "the last forward ran the encoder or the decoder only: use vae_backward_ex");
     if (part != 2) {
         if (backward_first<T>(c, x, params, grads, g_xhat, gscale, g_mu, g_lv, g_z, g_pre, kld_weight, add_kl, st)) return -1;
-        c->bwd_half_done = 1;
+        c->fwd.bwd_half_done = 1;
         if (part == 1) return join_sides(c, st);
-    } else if (!c->bwd_half_done) return vae_set_error("vae_backward", "part 2 before part 1");
-    c->bwd_half_done = 0;
+    } else if (!c->fwd.bwd_half_done) return vae_set_error("vae_backward", "part 2 before part 1");
+    c->fwd.bwd_half_done = 0;
     if (backward_second<T>(c, x, params, grads, gscale, g_mu, g_lv, g_z, g_pre, kld_weight, add_kl, st)) return -1;
     return join_comm(c, st);
 }
 
-// vae_backward_ex: differentiates the last forward of whichever kind (c->fwd_kind), train or eval mode
+// vae_backward_ex: differentiates the last forward of whichever kind (c->fwd.kind), train or eval mode
 template <typename T>
 int backward_ex_impl(vae_ctx* c, const float* x, const float* params, float* grads, const float* g_xhat, const float* gscale,
                      const float* g_mu, const float* g_lv, const float* g_z, const float* g_pre, float kld_weight, int add_kl,
                      float* dx, float* dz, hipStream_t st) {
-    if (!c->B) return vae_set_error("vae_backward_ex", "no forward to differentiate");
-    if (c->fwd_kind == 2) {
+    if (!c->fwd) return vae_set_error("vae_backward_ex", "no forward to differentiate");
+    if (c->fwd.kind == FwdRecord::DECODE) {
         if (add_kl) return vae_set_error("vae_backward_ex", "the last forward was decode-only: it has no target, so there is no standard ELBO (use_std must be 0)");
         if (g_mu || g_lv || g_z || g_pre || dx) return vae_set_error("vae_backward_ex", "the last forward was decode-only: only g_xhat and dz apply");
         if (backward_first<T>(c, x, params, grads, g_xhat, nullptr, nullptr, nullptr, nullptr, nullptr, kld_weight, 0, st, true)) return -1;
@@ -1165,7 +1154,7 @@ int backward_ex_impl(vae_ctx* c, const float* x, const float* params, float* gra
         return join_comm(c, st);
     }
     if (dz) return vae_set_error("vae_backward_ex", "dz is the input gradient of a decode-only forward");
-    if (c->fwd_kind == 1) {
+    if (c->fwd.kind == FwdRecord::ENCODE) {
         if (add_kl || g_xhat) return vae_set_error("vae_backward_ex", "the last forward was encode-only: there is no reconstruction (no g_xhat, use_std must be 0)");
         if (bwd_clear_stats(c, st)) return -1;
         if (backward_second<T>(c, x, params, grads, nullptr, g_mu, g_lv, nullptr, g_pre, kld_weight, 0, st, 1, dx)) return -1;
@@ -1178,9 +1167,9 @@ int backward_ex_impl(vae_ctx* c, const float* x, const float* params, float* gra
 
 template <typename T>
 int pre_latents_impl(vae_ctx* c, float* out, hipStream_t st) {
-    const long n = (long)c->B * c->F;
+    const long n = (long)c->fwd.B * c->F;
     hipLaunchKernelGGL((pre_latents_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                       reinterpret_cast<const T*>(c->lay[3].y), c->lay[3].block, kSlope, out, c->B, (int)c->F, c->s2);
+                       reinterpret_cast<const T*>(c->lay[3].y), c->lay[3].block, kSlope, out, c->fwd.B, (int)c->F, c->s2);
     LAUNCH_CHECK("pre_latents_kernel");
     return 0;
 }

@@ -216,16 +216,10 @@ class _GenericELBO(torch.autograd.Function):
         out3 = torch.empty(3, device=xhat.device, dtype=torch.float32)
         gx, gm, gl = torch.empty_like(xhat), torch.empty_like(mu), torch.empty_like(lv)
         with torch.cuda.device(xhat.device):
-            if kl[0] != _lib.KL_PLAIN:
-                _lib.check(_lib.lib().vae_elbo_generic_kl(xhat.data_ptr(), target.data_ptr(), mu.data_ptr(), lv.data_ptr(),
-                                                         xhat.numel(), mu.shape[0], mu.shape[1], float(kld_weight), int(recon),
-                                                         int(kl[0]), float(kl[1]), out3.data_ptr(), gx.data_ptr(), gm.data_ptr(),
-                                                         gl.data_ptr(), _stream_ptr(xhat.device)), "vae_elbo_generic_kl")
-            else:
-                _lib.check(_lib.lib().vae_elbo_generic_ex(xhat.data_ptr(), target.data_ptr(), mu.data_ptr(), lv.data_ptr(),
-                                                         xhat.numel(), mu.shape[0], mu.shape[1], float(kld_weight), int(recon),
-                                                         out3.data_ptr(), gx.data_ptr(), gm.data_ptr(), gl.data_ptr(),
-                                                         _stream_ptr(xhat.device)), "vae_elbo_generic_ex")
+            _lib.check(_lib.lib().vae_elbo_generic_kl(xhat.data_ptr(), target.data_ptr(), mu.data_ptr(), lv.data_ptr(),
+                                                     xhat.numel(), mu.shape[0], mu.shape[1], float(kld_weight), int(recon),
+                                                     int(kl[0]), float(kl[1]), out3.data_ptr(), gx.data_ptr(), gm.data_ptr(),
+                                                     gl.data_ptr(), _stream_ptr(xhat.device)), "vae_elbo_generic_kl")
         ctx.save_for_backward(gx, gm, gl)
         ctx.mark_non_differentiable(out3)
         return out3[0].clone(), out3
@@ -512,6 +506,27 @@ class VanillaVAE(nn.Module):
         if x.device != self._flat.device:
             raise RuntimeError("input and model are on different devices")
 
+    def _noise_seed(self, counter: int) -> int:
+        """Seed of the device-side noise (used when no eps is given): distinct per call AND per rank, so data-parallel
+        replicas draw independent noise like the reference's per-process torch generator (models.py:182)."""
+        return (int(self.eps_seed) + counter + _rank() * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+
+    def _checked_eps(self, eps: Tensor | None, B: int, dev):
+        if eps is None:
+            return None
+        eps = eps.detach().to(dev, torch.float32).contiguous()
+        if eps.shape != (B, self.latent_dim):
+            raise RuntimeError(f"eps must be [{B},{self.latent_dim}]")
+        return eps
+
+    def _pre_latents(self, ctx, B: int, dev, want: bool) -> Tensor:
+        """EncoderOutput.pre_latents of the forward the context holds ([B, 0] when not wanted).  Inside the device guard."""
+        if not want:
+            return torch.empty(B, 0, device=dev)
+        pre = torch.empty(B, self.flattened_size, device=dev)
+        _lib.check(_lib.lib().vae_pre_latents(ctx.handle, pre.data_ptr(), self._stream()), "vae_pre_latents")
+        return pre
+
     def _run_forward(self, x: Tensor, eps: Tensor | None, train: bool, want_pre: bool | None = None, defer_output: bool = False):
         self._check_input(x)
         x = x.detach().contiguous().float()
@@ -521,27 +536,16 @@ class VanillaVAE(nn.Module):
         mu = torch.empty(B, L, device=dev)
         lv = torch.empty(B, L, device=dev)
         z = torch.empty(B, L, device=dev)
-        if eps is not None:
-            eps = eps.detach().to(dev, torch.float32).contiguous()
-            if eps.shape != (B, L):
-                raise RuntimeError(f"eps must be [{B},{L}]")
+        eps = self._checked_eps(eps, B, dev)
         self._fwd_count += 1
-        # seed of the device-side reparameterisation noise (used when eps is None): distinct per step AND per rank, so
-        # data-parallel replicas draw independent noise like the reference's per-process torch generator (models.py:182)
-        seed = (int(self.eps_seed) + self._fwd_count + _rank() * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+        seed = self._noise_seed(self._fwd_count)
         with self._device_guard():
             _lib.check(_lib.lib().vae_forward(
                 ctx.handle, x.data_ptr(), B, self._flat.data_ptr(), self._bnflat.data_ptr(), self._nbt.data_ptr(),
                 _lib.ptr(eps), seed, (2 if (train and defer_output) else int(train)), xhat.data_ptr(), mu.data_ptr(),
                 lv.data_ptr(), z.data_ptr(), self._stream()), "vae_forward")
-            if want_pre is None:
-                want_pre = self.materialize_pre_latents
-            if want_pre:
-                pre = torch.empty(B, self.flattened_size, device=dev)
-                _lib.check(_lib.lib().vae_pre_latents(ctx.handle, pre.data_ptr(), self._stream()), "vae_pre_latents")
-            else:
-                pre = torch.empty(B, 0, device=dev)
-        self._last = dict(x=x, xhat=xhat, mu=mu, lv=lv, z=z, train=train, B=B)
+            pre = self._pre_latents(ctx, B, dev, self.materialize_pre_latents if want_pre is None else want_pre)
+        self._last = dict(kind="forward", x=x, xhat=xhat, mu=mu, lv=lv, z=z, train=train, B=B)
         return xhat, mu, lv, z, pre
 
     def _run_encode(self, x: Tensor, train: bool):
@@ -552,16 +556,12 @@ class VanillaVAE(nn.Module):
         ctx = self._context(B)
         mu, lv, z = (torch.empty(B, L, device=dev) for _ in range(3))
         self._fwd_count += 1
-        seed = (int(self.eps_seed) + self._fwd_count + _rank() * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+        seed = self._noise_seed(self._fwd_count)
         with self._device_guard():
             _lib.check(_lib.lib().vae_encode(
                 ctx.handle, x.data_ptr(), B, self._flat.data_ptr(), self._bnflat.data_ptr(), self._nbt.data_ptr(), 0, seed,
                 int(train), mu.data_ptr(), lv.data_ptr(), z.data_ptr(), self._stream()), "vae_encode")
-            if self.materialize_pre_latents:
-                pre = torch.empty(B, self.flattened_size, device=dev)
-                _lib.check(_lib.lib().vae_pre_latents(ctx.handle, pre.data_ptr(), self._stream()), "vae_pre_latents")
-            else:
-                pre = torch.empty(B, 0, device=dev)
+            pre = self._pre_latents(ctx, B, dev, self.materialize_pre_latents)
         self._last = dict(kind="encode", x=x, mu=mu, lv=lv, z=z, train=train, B=B)
         return mu, lv, pre
 
@@ -590,7 +590,7 @@ class VanillaVAE(nn.Module):
 
     def _run_backward(self, g_xhat, g_mu, g_lv, g_z, g_pre, g_handle, into_gflat: bool = False):
         last = self._last
-        if last is None or not last["train"] or last.get("kind", "forward") != "forward":
+        if last is None or not last["train"] or last["kind"] != "forward":
             raise RuntimeError("backward needs a train-mode forward of this model")
         c = lambda t: None if t is None else t.contiguous().float()  # noqa: E731
         g_xhat, g_mu, g_lv, g_z, g_pre, g_handle = map(c, (g_xhat, g_mu, g_lv, g_z, g_pre, g_handle))
@@ -620,7 +620,7 @@ class VanillaVAE(nn.Module):
         last = self._last
         if last is None:
             raise RuntimeError("backward needs a forward of this model")
-        kind = last.get("kind", "forward")
+        kind = last["kind"]
         c = lambda t: None if t is None else t.contiguous().float()  # noqa: E731
         g_xhat, g_mu, g_lv, g_z, g_pre, g_handle = map(c, (g_xhat, g_mu, g_lv, g_z, g_pre, g_handle))
         B = last["B"]
@@ -751,7 +751,7 @@ class VanillaVAE(nn.Module):
             eps = eps.detach().to(dev, torch.float32).contiguous()
         if seed is None:
             self._ll_count = getattr(self, "_ll_count", 0) + 1
-            seed = int(self.eps_seed) + self._ll_count + _rank() * 0x9E3779B97F4A7C15
+            seed = self._noise_seed(self._ll_count)
         seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         log_w = torch.empty(K, B, device=dev, dtype=torch.float64)
         ll = torch.empty(B, device=dev, dtype=torch.float64)
@@ -816,7 +816,7 @@ class VanillaVAE(nn.Module):
         stay on the device.  With kl_free_bits / kl_capacity set it is the very reduction the step's mask was decided on.  Data
         parallel: the replica's own batch."""
         self._require_device()
-        if self._last is None or self._last.get("kind", "forward") == "decode" or self._ctx is None:
+        if self._last is None or self._last["kind"] == "decode" or self._ctx is None:
             raise RuntimeError("kl_per_dim needs a forward, fused step or encode of this model")
         out = torch.empty(self.latent_dim, device=self._flat.device, dtype=torch.float64)
         with self._device_guard():
@@ -881,10 +881,7 @@ class VanillaVAE(nn.Module):
         ctx = self._context(B)
         if eps is None and not use_device_eps:
             eps = torch.randn(B, L, device=dev, dtype=torch.float32)
-        if eps is not None:
-            eps = eps.detach().to(dev, torch.float32).contiguous()
-            if eps.shape != (B, L):
-                raise RuntimeError(f"eps must be [{B},{L}]")
+        eps = self._checked_eps(eps, B, dev)
         bufs = self.__dict__.get("_step_bufs")
         if bufs is None or bufs[0] != (B, dev):
             bufs = ((B, dev), torch.empty(B, 1, self.img_size, self.img_size, device=dev), torch.empty(B, L, device=dev),
@@ -892,7 +889,7 @@ class VanillaVAE(nn.Module):
             self.__dict__["_step_bufs"] = bufs
         _, xhat, mu, lv, z, out3 = bufs
         self._fwd_count += 1
-        seed = (int(self.eps_seed) + self._fwd_count + _rank() * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+        seed = self._noise_seed(self._fwd_count)
         n, offs, sizes, lrs, b1s, beta2, adam_eps, wd = optimizer._step_args()
         clip = optimizer._clip_args()   # (max_grad_norm / skip_nonfinite: norm, decision and step count on the device)
         self._bwd_kld_weight = float(self.kld_weight)
@@ -911,7 +908,7 @@ class VanillaVAE(nn.Module):
                     n, offs, sizes, lrs, b1s, beta2, adam_eps, wd, float(optimizer.grad_scale), optimizer._step + 1, int(exchange),
                     xhat.data_ptr(), mu.data_ptr(), lv.data_ptr(), z.data_ptr(), out3.data_ptr(), self._stream()), "vae_train_step_fused")
         optimizer._stepped()
-        self._last = dict(x=x, xhat=xhat, mu=mu, lv=lv, z=z, train=True, B=B)
+        self._last = dict(kind="forward", x=x, xhat=xhat, mu=mu, lv=lv, z=z, train=True, B=B)
         params, views = self._param_grad_views()
         if params[0].grad is not views[0] or params[-1].grad is not views[-1]:   # (bound once: the fused path never unbinds them)
             self.bind_flat_grads()
