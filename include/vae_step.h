@@ -151,18 +151,38 @@ int vae_elbo_generic_ex(const float* xhat, const float* target, const float* mu,
 #define VAE_KL_PLAIN 0
 #define VAE_KL_FREE_BITS 1
 #define VAE_KL_CAPACITY 2
+/*   VAE_KL_TC         T = KL + (param - 1) TC, param = tc_weight >= 0 (beta-TCVAE, Chen et al. 2018, in the form KL + (beta - 1) TC):
+ *                     TC = 1/B sum_i [log q(z_i) - sum_d log q(z_id)] with q the in-batch mixture 1/B sum_j N(mu_j, diag e^{log_var_j}),
+ *                     the query's own component included, at the forward's own z_i = mu_i + eps_i exp(log_var_i / 2) - the quantity
+ *                     vae_latent_stats reports as tc for eps = the forward's.  Pairwise kernels beside the decoder compute TC and its
+ *                     gradient through both the queries and the components (total_corr.cuh), every sum in a fixed order; the backward adds
+ *                     kld_weight (param - 1) dTC/d(mu, log_var) to the plain KL gradient.  Batches of at most 4096; TC is 0 for a batch
+ *                     of 1 and for latent_dim 1.  Work space 4 B^2 + O(B latent_dim) bytes, allocated by the first such forward.  f16
+ *                     storage: this term shares the power-of-two gradient scale of the rest and is not bounded by the KL gradient. */
+#define VAE_KL_TC 3
 /* KL objective for the following forwards of this context (sticky; default plain).  A forward records kind and param: its loss,
  * deferred loss and backward (vae_backward, _part, _ex with use_std = 1, the training steps) use the recorded ones even if the
  * setting changes after.  A NaN, negative or infinite param, or VAE_KL_FREE_BITS with param <= 0, returns -1.  Enqueues nothing:
  * a per-step capacity ramp may call it every step. */
 int vae_set_kl_objective(vae_ctx* ctx, int kind, double param);
-/* vae_elbo_generic_ex with the KL objective chosen per call: g_mu / g_log_var are the gradients of kld_weight * T. */
+/* vae_elbo_generic_ex with the KL objective chosen per call: g_mu / g_log_var are the gradients of kld_weight * T.  VAE_KL_TC
+ * returns -1: the term needs the eps of the forward, which this entry point does not take (vae_total_correlation does). */
 int vae_elbo_generic_kl(const float* xhat, const float* target, const float* mu, const float* log_var, int64_t n,
                         int batch, int latent_dim, float kld_weight, int recon, int kl_kind, double kl_param, float* out3,
                         float* g_xhat, float* g_mu, float* g_log_var, vae_stream_t stream);
 /* kl_d [latent_dim] f64 of the last forward (vae_forward, the training steps, vae_encode), device memory, no host
  * synchronisation: the forward's own reduction when it ran with an objective other than plain, else reduced on demand. */
 int vae_kl_per_dim(vae_ctx* ctx, double* out, vae_stream_t stream);
+/* Total correlation (nats, VAE_KL_TC's definition) of `batch` posteriors [batch, latent_dim] f32 at z = mu + eps exp(log_var / 2), and
+ * optionally its gradient: tc one f64, g_mu / g_log_var [batch, latent_dim] f32 = dTC/dmu, dTC/dlog_var (through z as well), each may
+ * be NULL.  Device memory, no host synchronisation, context-free; the kernels of the VAE_KL_TC objective, every sum in a fixed order
+ * (repeated calls are bit-identical).  Work space 4 batch^2 + 32 batch latent_dim bytes from the stream-ordered allocator.  Returns -1
+ * before anything is enqueued for a NULL mu / log_var / eps / tc, batch outside 1..4096 or latent_dim outside 1..4096. */
+int vae_total_correlation(const float* mu, const float* log_var, const float* eps, int batch, int latent_dim, double* tc,
+                          float* g_mu, float* g_log_var, vae_stream_t stream);
+/* TC of the last forward (vae_forward, the training steps, vae_encode; an error after vae_decode or with no forward), one device f64,
+ * no host synchronisation: the forward's own value when it ran with VAE_KL_TC, else computed on demand as vae_kl_per_dim does. */
+int vae_last_total_correlation(vae_ctx* ctx, double* out, vae_stream_t stream);
 
 /* Importance-weighted log-likelihood (IWAE_K) and per-sample ELBO of x under the model in eval mode.
  * eps [K,B,L] f32 or NULL (device counter generator, seed, stream 6; index (k*B+b)*L+l).
@@ -343,7 +363,9 @@ int vae_debug_stamps(vae_ctx* ctx, const char* tag, int epi, long long* out);
 /* Debug / test hooks: copy an internal NHWC tensor to f32 NCHW.  which: 0..7 raw conv output
  * of BN layer i, 8..15 its dz, 16 decoder_input output, 17 its gradient; 18 the latent gradient of the last backward,
  * [B, 2 latent_dim] f32 (dmu | dlog_var per row, times the f16 gradient scale), and 19 the per-dimension factors [latent_dim] f32 of the last
- * forward's KL objective (an error after a plain forward), both copied as they are. */
+ * forward's KL objective (an error after a plain forward), both copied as they are; 20 the gradient of the last forward's total
+ * correlation, [B, 2 latent_dim] f32 (g_mu | g_log_var per row) before any weight or scale (computed on demand as
+ * vae_last_total_correlation does). */
 int vae_debug_tensor(vae_ctx* ctx, int which, float* out, int64_t capacity, vae_stream_t stream);
 /* hardware self-test of the transposed LDS read used by the bf16 weight-gradient kernel */
 int vae_selftest_tr16(vae_stream_t stream);

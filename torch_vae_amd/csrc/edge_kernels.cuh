@@ -478,11 +478,14 @@ struct LatentBwdArgs {
     int B, L; float kld_weight; int add_kl;
     float gmul;                           // every upstream gradient entering here is multiplied by it (f16 gradient scaling; 1 otherwise)
     const float* factor;                  // SHAPED only: per-dimension factor of the KL objective [L] (kl_shape_kernel)
+    const float* tcg; float tcw;          // TC only: the total-correlation gradient [B][2L] (g_mu | g_log_var, tc_comp_kernel) and tc_weight - 1
 };
 // SHAPED: the KL contribution of dimension l is multiplied by factor[l] (free bits: 0 below the floor, capacity: sign(KL - C)).
 // The factor is 0 or +-1, so it changes no magnitude: the power-of-two gradient scaling of f16 storage (gmul / ginv) is untouched.
 // The plain objective launches the SHAPED = false instantiation, whose code is what it was before the objectives existed.
-template <bool SHAPED>
+// TC (VAE_KL_TC): T = KL + (tc_weight - 1) TC, so the plain KL gradient stays and gs * kld_weight * (tc_weight - 1) * dTC/d(mu, log_var)
+// joins it.  This term is not bounded by the KL gradient: with f16 storage it rides on the same power-of-two scale gmul as the rest.
+template <bool SHAPED, bool TC = false>
 static __global__ void latent_bwd_kernel(LatentBwdArgs a) {   // LAT_LANES lanes per (b,l)
     const int i = (blockIdx.x * blockDim.x + threadIdx.x) / LAT_LANES, sub = threadIdx.x & (LAT_LANES - 1);
     const bool ok = i < a.B * a.L;
@@ -505,6 +508,10 @@ static __global__ void latent_bwd_kernel(LatentBwdArgs a) {   // LAT_LANES lanes
         float k = gs * a.kld_weight / (float)a.B;
         if constexpr (SHAPED) k *= a.factor[l];
         dmu += k * m; dlv += k * 0.5f * (expf(v) - 1.f);
+        if constexpr (TC) {
+            const float kt = gs * a.kld_weight * a.tcw;
+            dmu += kt * a.tcg[(size_t)b * 2 * a.L + l]; dlv += kt * a.tcg[(size_t)b * 2 * a.L + a.L + l];
+        }
     }
     if (a.gmu) dmu += a.gmu[i] * a.gmul;
     if (a.glv) dlv += a.glv[i] * a.gmul;

@@ -7,6 +7,7 @@
 #include "loglik.cuh"
 #include "latent_stats.cuh"
 #include "grad_clip.cuh"
+#include "total_corr.cuh"
 
 static thread_local std::string g_err;
 int vae_set_error(const char* what, const char* why) {
@@ -363,6 +364,7 @@ extern "C" int vae_forward(vae_ctx* c, const float* x, int B, const float* param
     if (!c) return vae_set_error("vae_forward", "null ctx");
     if (B < 1 || B > c->maxB) return vae_set_error("vae_forward", "batch exceeds the context's max_batch");
     if (!x || !params || !xhat || !mu || !lv || !z) return vae_set_error("vae_forward", "null tensor pointer");
+    if (c->kl_kind == VAE_KL_TC && B > TC_MAX_B) return vae_set_error("vae_forward", "the total-correlation objective (VAE_KL_TC) takes batches of at most 4096");
     hipStream_t st = (hipStream_t)stream;
     if (begin_forward(c, FwdRecord::FULL, B, train, st)) return -1;
     c->fwd.x = x; c->fwd.xhat = xhat; c->fwd.mu = mu; c->fwd.lv = lv; c->fwd.z = z;
@@ -469,15 +471,16 @@ extern "C" int vae_set_recon_loss(vae_ctx* c, int kind) {
 }
 
 // ---- KL objectives (free bits, capacity target; edge_kernels.cuh: kl_shape_kernel) ---------------------------------------------
-static int check_kl_objective(const char* what, int kind, double param) {
-    if (kind != VAE_KL_PLAIN && kind != VAE_KL_FREE_BITS && kind != VAE_KL_CAPACITY) return vae_set_error(what, "kind must be VAE_KL_PLAIN, VAE_KL_FREE_BITS or VAE_KL_CAPACITY");
+static int check_kl_objective(const char* what, int kind, double param, bool allow_tc = false) {
+    if (kind == VAE_KL_TC && !allow_tc) return vae_set_error(what, "VAE_KL_TC needs the eps of the forward, which this entry point does not have: use vae_total_correlation for the term and its gradient");
+    if (kind != VAE_KL_PLAIN && kind != VAE_KL_FREE_BITS && kind != VAE_KL_CAPACITY && kind != VAE_KL_TC) return vae_set_error(what, "kind must be VAE_KL_PLAIN, VAE_KL_FREE_BITS, VAE_KL_CAPACITY or VAE_KL_TC");
     if (param != param || param < 0.0 || std::isinf(param)) return vae_set_error(what, "the parameter must be finite and >= 0");
     if (kind == VAE_KL_FREE_BITS && !(param > 0.0)) return vae_set_error(what, "free bits need lambda > 0 nats per dimension");
     return 0;
 }
 extern "C" int vae_set_kl_objective(vae_ctx* c, int kind, double param) {
     if (!c) return vae_set_error("vae_set_kl_objective", "null ctx");
-    if (check_kl_objective("vae_set_kl_objective", kind, param)) return -1;
+    if (check_kl_objective("vae_set_kl_objective", kind, param, true)) return -1;
     c->kl_kind = kind; c->kl_param = kind == VAE_KL_PLAIN ? 0.0 : param;
     return 0;
 }
@@ -495,17 +498,19 @@ static int enqueue_kl_shape(const float* mu, const float* lv, int B, int L, int 
 int launch_kl_shape(vae_ctx* c, hipStream_t st) {
     if (!c->kl_ws) {
         c->kl_ws = dalloc<char>(c, (size_t)c->L * 12 + 16); c->kl_tk = dalloc<unsigned>(c, 4);
-        if (!c->kl_ws || !c->kl_tk || hipEventCreateWithFlags(&c->ev_kl, hipEventDisableTiming) != hipSuccess) { c->kl_ws = nullptr; return vae_set_error("kl_shape", "allocation failed"); }
+        if (!c->kl_ws || !c->kl_tk || (!c->ev_kl && hipEventCreateWithFlags(&c->ev_kl, hipEventDisableTiming) != hipSuccess)) { c->kl_ws = nullptr; return vae_set_error("kl_shape", "allocation failed"); }
     }
+    // (the total-correlation objective takes the plain reduction: kl_d and KL; tc_final_kernel then writes T)
+    const int kind = c->fwd.kl_kind == VAE_KL_TC ? VAE_KL_PLAIN : c->fwd.kl_kind;
     // always the same side stream: successive reductions of a context write the same buffers and must not overlap
     SideFork f = fork_side(c, st, vae_ctx::KL_SIDE);
     if (f.rc) return f.rc;
     {
         ProfScope ps(c, "kl_shape", 8.0 * c->fwd.B * c->L + 12.0 * c->L, 0, f.st);
-        if (enqueue_kl_shape(c->fwd.mu, c->fwd.lv, c->fwd.B, c->L, c->fwd.kl_kind, c->fwd.kl_param, c->kl_d(), c->kl_scal(), c->kl_factor(), c->kl_tk, f.st)) return -1;
+        if (enqueue_kl_shape(c->fwd.mu, c->fwd.lv, c->fwd.B, c->L, kind, c->fwd.kl_param, c->kl_d(), c->kl_scal(), c->kl_factor(), c->kl_tk, f.st)) return -1;
     }
     HIP_CHECK_RET(hipEventRecord(c->ev_kl, f.st));
-    c->fwd.kl_pending = 1;
+    c->fwd.kl_pending = 1; c->fwd.kl_reduced = 1;
     return 0;
 }
 int join_kl(vae_ctx* c, hipStream_t st) {
@@ -516,9 +521,114 @@ extern "C" int vae_kl_per_dim(vae_ctx* c, double* out, vae_stream_t stream) {
     if (!c || !c->fwd || !c->fwd.mu || !c->fwd.lv) return vae_set_error("vae_kl_per_dim", "no forward with a posterior (vae_forward, a training step or vae_encode)");
     if (!out) return vae_set_error("vae_kl_per_dim", "null output pointer");
     hipStream_t st = (hipStream_t)stream;
-    if (!c->fwd.kl_pending && launch_kl_shape(c, st)) return -1;   // (the forward was plain: reduce now)
+    if (!c->fwd.kl_reduced && launch_kl_shape(c, st)) return -1;   // (the forward was plain: reduce now)
     if (join_kl(c, st)) return -1;
     HIP_CHECK_RET(hipMemcpyAsync(out, c->kl_d(), (size_t)c->L * 8, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+// ---- total correlation (total_corr.cuh) --------------------------------------------------------------------------------------
+// The six launches on `st`.  c: profiling labels only (null: the context-free entry point).  gmu / glv null: value only.
+static int enqueue_tc(vae_ctx* c, const float* mu, const float* lv, const float* eps, int B, int L, const TcWork& w, double* tc_out,
+                      float* gmu, float* glv, int ldo, double* scal, double tc_weight, hipStream_t st) {
+    const double bl = (double)B * L, bb = (double)B * B;
+    TcSideArgs a; a.z = w.z; a.mu = mu; a.hw = w.hw; a.c2 = w.c2; a.A = w.A; a.lse = w.lse; a.lsed = w.lsed; a.gz = w.gz; a.lv = lv; a.eps = eps;
+    a.part = w.part; a.gmu = gmu; a.glv = glv; a.ldo = ldo; a.B = B; a.L = L; a.grad = (gmu || glv) ? 1 : 0;
+    const unsigned tiles = (unsigned)((B + TC_TILE - 1) / TC_TILE);
+    {
+        ProfScope ps(c, "tc_prep", 24.0 * bl, 0, st);
+        hipLaunchKernelGGL(tc_prep_kernel, dim3((B + 3) / 4), dim3(256), 0, st, mu, lv, eps, B, L, w.z, w.hw, w.c2, w.cj);
+        LAUNCH_CHECK("tc_prep_kernel");
+    }
+    {
+        ProfScope ps(c, "tc_pair", 12.0 * bl + 4.0 * bb, 3.0 * bb * L, st);
+        hipLaunchKernelGGL(tc_pair_kernel, dim3(tiles, tiles), dim3(256), 0, st, w.z, mu, w.hw, w.cj, B, L, w.A);
+        LAUNCH_CHECK("tc_pair_kernel");
+    }
+    {
+        ProfScope ps(c, "tc_row", 4.0 * bb, 0, st);
+        hipLaunchKernelGGL(tc_row_kernel, dim3((B + 3) / 4), dim3(256), 0, st, w.A, B, w.lse);
+        LAUNCH_CHECK("tc_row_kernel");
+    }
+    {
+        ProfScope ps(c, "tc_query", 24.0 * bl + 4.0 * bb, (a.grad ? 14.0 : 5.0) * bb * L, st);
+        hipLaunchKernelGGL(tc_query_kernel, dim3(w.npart), dim3(256), 0, st, a);
+        LAUNCH_CHECK("tc_query_kernel");
+    }
+    if (a.grad) {
+        ProfScope ps(c, "tc_comp", 36.0 * bl + 4.0 * bb, 12.0 * bb * L, st);
+        hipLaunchKernelGGL(tc_comp_kernel, dim3(w.npart), dim3(256), 0, st, a);
+        LAUNCH_CHECK("tc_comp_kernel");
+    }
+    ProfScope ps(c, "tc_final", 4.0 * B + 8.0 * w.npart, 0, st);
+    hipLaunchKernelGGL(tc_final_kernel, dim3(1), dim3(256), 0, st, w.lse, w.part, w.npart, B, L, tc_out, scal, tc_weight);
+    LAUNCH_CHECK("tc_final_kernel");
+    return 0;
+}
+extern "C" int vae_total_correlation(const float* mu, const float* lv, const float* eps, int B, int L, double* tc, float* g_mu,
+                                     float* g_lv, vae_stream_t stream) {
+    if (!mu || !lv || !eps || !tc) return vae_set_error("vae_total_correlation", "null pointer (mu, log_var, eps, tc)");
+    if (B < 1 || B > TC_MAX_B) return vae_set_error("vae_total_correlation", "batch must be in 1..4096");
+    if (L < 1 || L > 4096) return vae_set_error("vae_total_correlation", "latent_dim must be in 1..4096");
+    hipStream_t st = (hipStream_t)stream;
+    void* ws = nullptr;
+    HIP_CHECK_RET(hipMallocAsync(&ws, tc_carve(nullptr, B, L, nullptr), st));
+    TcWork w; tc_carve(ws, B, L, &w);
+    const int rc = enqueue_tc(nullptr, mu, lv, eps, B, L, w, tc, g_mu, g_lv, L, nullptr, 0.0, st);
+    const hipError_t fe = hipFreeAsync(ws, st);
+    if (rc) return rc;
+    if (fe != hipSuccess) return vae_set_error("hipFreeAsync", hipGetErrorString(fe));
+    return 0;
+}
+// The context's work space: the gradient [B][2L] (g_mu | g_log_var) in front, the kernels' pieces behind it; sized for the largest
+// batch a forward has asked for so far (a larger one frees and allocates again, behind a device synchronisation).
+static size_t tc_grad_bytes(int B, int L) { return (size_t)align_up((int64_t)B * 2 * L * 4, 256); }
+static int tc_reserve(vae_ctx* c, int B) {
+    if (c->tc_ws && c->tc_ws_B >= B) return 0;
+    if (c->tc_ws) {
+        HIP_CHECK_RET(hipDeviceSynchronize());
+        HIP_CHECK_RET(hipFree(c->tc_ws));
+        c->allocs.erase(std::remove(c->allocs.begin(), c->allocs.end(), c->tc_ws), c->allocs.end());
+        c->ws_bytes -= (int64_t)c->tc_ws_bytes; c->tc_ws = nullptr; c->tc_ws_B = 0; c->tc_ws_bytes = 0;
+    }
+    const size_t need = tc_grad_bytes(B, c->L) + tc_carve(nullptr, B, c->L, nullptr);
+    c->tc_ws = dalloc<char>(c, need);
+    if (!c->tc_ws) return vae_set_error("total correlation", "hipMalloc of the work space failed");
+    c->tc_ws_B = B; c->tc_ws_bytes = std::max<size_t>(need, 256);
+    return 0;
+}
+static TcWork tc_work(vae_ctx* c) {
+    TcWork w; tc_carve(static_cast<char*>(c->tc_ws) + tc_grad_bytes(c->fwd.B, c->L), c->fwd.B, c->L, &w);
+    return w;
+}
+// TC of the held forward and its gradient on side stream KL_SIDE (behind kl_shape_kernel when the forward's objective is VAE_KL_TC:
+// tc_final_kernel then turns the KL it left into T); ev_kl follows, as for launch_kl_shape
+int launch_tc(vae_ctx* c, hipStream_t st) {
+    const int B = c->fwd.B, L = c->L;
+    if (B > TC_MAX_B) return vae_set_error("total correlation", "the batch exceeds 4096");
+    if (tc_reserve(c, B)) return -1;
+    if (!c->ev_kl && hipEventCreateWithFlags(&c->ev_kl, hipEventDisableTiming) != hipSuccess) { c->ev_kl = nullptr; return vae_set_error("total correlation", "event creation failed"); }
+    SideFork f = fork_side(c, st, vae_ctx::KL_SIDE);
+    if (f.rc) return f.rc;
+    const TcWork w = tc_work(c);
+    const bool objective = c->fwd.kl_kind == VAE_KL_TC;
+    if (enqueue_tc(c, c->fwd.mu, c->fwd.lv, c->eps, B, L, w, w.tc, c->tc_grad(), c->tc_grad() + L, 2 * L, objective ? c->kl_scal() : nullptr,
+                   c->fwd.kl_param, f.st)) return -1;
+    HIP_CHECK_RET(hipEventRecord(c->ev_kl, f.st));
+    c->fwd.kl_pending = 1; c->fwd.tc_done = 1;
+    return 0;
+}
+// the held forward's TC is in the work space (its own launch, or one made now) and ordered in front of `st`
+static int ensure_tc(const char* what, vae_ctx* c, hipStream_t st) {
+    if (!c || !c->fwd || !c->fwd.mu || !c->fwd.lv) return vae_set_error(what, "no forward with a posterior (vae_forward, a training step or vae_encode)");
+    enter(c, st);
+    if (!c->fwd.tc_done && launch_tc(c, st)) return -1;
+    return join_kl(c, st);
+}
+extern "C" int vae_last_total_correlation(vae_ctx* c, double* out, vae_stream_t stream) {
+    if (!out) return vae_set_error("vae_last_total_correlation", "null output pointer");
+    if (ensure_tc("vae_last_total_correlation", c, (hipStream_t)stream)) return -1;
+    HIP_CHECK_RET(hipMemcpyAsync(out, tc_work(c).tc, 8, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
 }
 
@@ -1009,6 +1119,13 @@ extern "C" int vae_debug_tensor(vae_ctx* c, int which, float* out, int64_t capac
         if (c->L > capacity) return vae_set_error("vae_debug_tensor", "output too small");
         if (join_kl(c, (hipStream_t)stream)) return -1;
         HIP_CHECK_RET(hipMemcpyAsync(out, c->kl_factor(), (size_t)c->L * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        return 0;
+    }
+    if (which == 20) {   // the gradient of the last forward's total correlation [B, 2L] f32 (g_mu | g_log_var), before any weight or scale
+        const long n = (long)c->fwd.B * 2 * c->L;
+        if (n > capacity) return vae_set_error("vae_debug_tensor", "output too small");
+        if (ensure_tc("vae_debug_tensor", c, (hipStream_t)stream)) return -1;
+        HIP_CHECK_RET(hipMemcpyAsync(out, c->tc_grad(), (size_t)n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
         return 0;
     }
     if (which >= 0 && which < 16) { const BnLayer& l = c->lay[which & 7]; src = which < 8 ? l.y : l.dz; C = l.C; HW = l.H * l.W; }

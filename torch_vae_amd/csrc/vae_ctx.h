@@ -60,7 +60,7 @@ struct WgradKnobs { int wgs, cap_mb, tile, wide, wide_wgs, small_wgs = 1024, mid
 
 // The last forward of a context: which one ran, with what settings, and what it left for vae_loss* / vae_backward* to consume.
 // Exactly two functions change which forward is held: begin_forward and drop_forward (below).  Besides them the record is written
-// where a forward's product is made or consumed: decode_impl (the output conv ran or was deferred), launch_kl_shape (kl_pending),
+// where a forward's product is made or consumed: decode_impl (the output conv ran or was deferred), launch_kl_shape (kl_pending), launch_tc (tc_done),
 // backward_first (convout_pending / dlogit_valid / loss_out3), bwd_clear_stats (bwd_dirty), backward_impl (bwd_half_done),
 // vae_loss_deferred (loss_out3 / loss_kw of a deferred output conv) and launch_conv_pipe (walk_dir).
 struct FwdRecord {
@@ -70,7 +70,9 @@ struct FwdRecord {
     // settings the forward ran with (vae_set_recon_loss / vae_set_kl_objective at that time): its deferred output conv, loss and
     // backward use these, whatever the context's settings are by then.  Kinds without an ELBO record VAE_KL_PLAIN.
     int recon = VAE_RECON_BCE, kl_kind = VAE_KL_PLAIN; double kl_param = 0.0;
-    int kl_pending = 0;                          // kl_shape_kernel of this forward is in flight on side stream KL_SIDE: consumers wait for ev_kl
+    int kl_pending = 0;                          // kl_shape_kernel / the tc_* kernels of this forward are in flight on side stream KL_SIDE: consumers wait for ev_kl
+    int kl_reduced = 0;                          // kl_shape_kernel ran for this forward: kl_d and KL are in kl_ws (behind ev_kl)
+    int tc_done = 0;                             // this forward's total correlation and its gradient are in tc_ws (launch_tc; behind ev_kl as well)
     const float* x = nullptr; float *xhat = nullptr, *mu = nullptr, *lv = nullptr, *z = nullptr;   // the caller's tensors (null: the kind has none)
     // f16 storage: the backward runs on gradients multiplied by gmul (a power of two chosen per forward so that the stored
     // dz stay inside the f16 range: the BCE mean makes them O(1/(B*H*W))); every parameter gradient is written times ginv.
@@ -117,6 +119,10 @@ struct vae_ctx {
     double* kl_scal() const { return reinterpret_cast<double*>(kl_d() + L); }
     float* kl_factor() const { return reinterpret_cast<float*>(kl_scal() + 2); }
     const double* kl_shaped() const { return fwd.kl_kind != VAE_KL_PLAIN ? kl_scal() : nullptr; }   // loss_finalize_kernel's argument
+    // tc_ws (allocated on first use, for the largest batch asked for so far): the total-correlation gradient [B][2L] f32 | the
+    // work space of the tc_* kernels (total_corr.cuh), written on side stream KL_SIDE by launch_tc
+    void* tc_ws = nullptr; size_t tc_ws_bytes = 0; int tc_ws_B = 0;
+    float* tc_grad() const { return static_cast<float*>(tc_ws); }
     // vae_log_likelihood: ps_part (non-null only during its decoder passes) switches the output conv to its per-sample mode
     // (tile partials, target x[b mod ps_tb]; ps_ntile: tiles per image of the kernel taken).  ll_*: its scratch, allocated on first use.
     double* ps_part = nullptr; int ps_tb = 0, ps_ntile = 0;
@@ -194,7 +200,7 @@ static inline void enter(vae_ctx* c, hipStream_t st) { c->cur_stream = st; c->cu
 static inline void drop_forward(vae_ctx* c) {
     FwdRecord& f = c->fwd;
     f.kind = FwdRecord::NONE; f.B = 0; f.trained = 0;
-    f.kl_pending = 0; f.convout_pending = 0; f.dlogit_valid = 0; f.loss_out3 = nullptr; f.bwd_half_done = 0;
+    f.kl_pending = 0; f.kl_reduced = 0; f.tc_done = 0; f.convout_pending = 0; f.dlogit_valid = 0; f.loss_out3 = nullptr; f.bwd_half_done = 0;
 }
 // A forward of `kind` over B images starts on `st`: the previous one is gone, the settings are snapshotted, and the statistics'
 // memset is the first thing enqueued on `st`.  The entry point then records the caller tensors this kind has (the rest stay null).
@@ -221,6 +227,7 @@ int join_comm(vae_ctx* c, hipStream_t st);
 // wait a consumer's stream needs before it reads the factors / scalars (nothing when no reduction is outstanding)
 int launch_kl_shape(vae_ctx* c, hipStream_t st);
 int join_kl(vae_ctx* c, hipStream_t st);
+int launch_tc(vae_ctx* c, hipStream_t st);   // total correlation of the held forward and its gradient, same stream and event (vae_api.hip)
 int launch_loss_finalize(vae_ctx* c, float* out3, float kld_weight, hipStream_t st);   // loss_finalize_kernel for the last forward (vae_api.hip)
 
 // entry points instantiated once per storage type (impl_bf16.hip, impl_f16.hip, impl_f32.hip)

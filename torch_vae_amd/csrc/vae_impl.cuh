@@ -641,6 +641,8 @@ int forward_impl(vae_ctx* c, const float* x, int B, const float* params, float* 
     if (rc) return rc;
     // free bits / capacity target: the batch reduction its loss and backward need, beside the decoder (nothing for the plain objective)
     if (c->fwd.kl_kind != VAE_KL_PLAIN && launch_kl_shape(c, st)) return -1;
+    // total-correlation objective: the pairwise pass and its backward follow on the same side stream
+    if (c->fwd.kl_kind == VAE_KL_TC && launch_tc(c, st)) return -1;
     return decode_impl<T>(c, z, B, params, bn_running, nbt, train, x, xhat, st);
 }
 
@@ -975,8 +977,12 @@ static int backward_second(vae_ctx* c, const float* x, const float* params, floa
         LatentBwdArgs lb;
         lb.slab = c->slab; lb.nslab = nsplit; lb.npad = c->npad_di; lb.mu = c->fwd.mu; lb.lv = c->fwd.lv; lb.eps = c->eps; lb.gscale = gscale;
         lb.gmu = g_mu; lb.glv = g_lv; lb.gz = g_z; lb.dlat = c->dlat; lb.B = B; lb.L = L; lb.kld_weight = kld_weight; lb.add_kl = add_kl; lb.gmul = c->fwd.gmul;
-        lb.factor = nullptr;
-        if (add_kl && c->fwd.kl_kind != VAE_KL_PLAIN) {   // the objective the forward recorded: its per-dimension factors
+        lb.factor = nullptr; lb.tcg = nullptr; lb.tcw = 0.f;
+        if (add_kl && c->fwd.kl_kind == VAE_KL_TC) {      // the plain KL gradient plus (tc_weight - 1) times the TC gradient of tc_comp_kernel
+            if (join_kl(c, st)) return -1;
+            lb.tcg = c->tc_grad(); lb.tcw = (float)(c->fwd.kl_param - 1.0);
+            hipLaunchKernelGGL((latent_bwd_kernel<false, true>), dim3((B * L * LAT_LANES + 255) / 256), dim3(256), 0, st, lb);
+        } else if (add_kl && c->fwd.kl_kind != VAE_KL_PLAIN) {   // the objective the forward recorded: its per-dimension factors
             if (join_kl(c, st)) return -1;
             lb.factor = c->kl_factor();
             hipLaunchKernelGGL(latent_bwd_kernel<true>, dim3((B * L * LAT_LANES + 255) / 256), dim3(256), 0, st, lb);

@@ -36,6 +36,26 @@ Deviations from the reference, all explicit:
     ``kl_d`` and ``KL`` are the replica's OWN batch means (as BatchNorm
     statistics are per replica), so replicas may mask different dimensions in
     a step; the all-reduce averages the resulting gradients.
+  * ``tc_weight`` (keyword-only; default ``None`` = off) is the beta-TCVAE
+    objective (Chen et al. 2018) in the form ``KL + (tc_weight - 1) * TC``:
+    ``TC = mean_i [log q(z_i) - sum_d log q(z_id)]`` over the in-batch
+    mixture ``q``, the query's own component included, at the forward's own
+    ``z`` - what ``latent_statistics(mu, log_var, eps=eps[None]).tc`` reports.
+    An alternative to ``kl_free_bits`` / ``kl_capacity``; read at every
+    forward and fused step; batches of at most 4096.  ``total_correlation()``
+    returns the value of the last forward.  Data parallel: TC is over the
+    replica's OWN batch, as ``kl_d`` and the BatchNorm statistics are.
+
+  KL term ``T`` of ``loss = reconstruction + kld_weight * T``:
+
+    ===================  =============================  ==================
+    option               T                              KL gradient
+    ===================  =============================  ==================
+    (none)               KL                             plain
+    ``kl_free_bits=l``   sum_d max(kl_d, l)             0 where kl_d <= l
+    ``kl_capacity=C``    |KL - C|                       times sign(KL - C)
+    ``tc_weight=b``      KL + (b - 1) TC                plain + (b - 1) dTC
+    ===================  =============================  ==================
 """
 from __future__ import annotations
 
@@ -64,13 +84,18 @@ def _recon_kind(name) -> int:
     return kind
 
 
-def _kl_objective(free_bits, capacity) -> tuple[int, float]:
-    """(VAE_KL_* kind, parameter) of the kl_free_bits / kl_capacity pair; ValueError on anything the library would refuse."""
+def _kl_objective(free_bits, capacity, tc_weight=None) -> tuple[int, float]:
+    """(VAE_KL_* kind, parameter) of the kl_free_bits / kl_capacity / tc_weight triple; ValueError on anything the library would refuse."""
     def number(v, name):
         if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
             raise ValueError(f"{name} must be a finite number >= 0, got {v!r}")
         return float(v)
     fb = number(free_bits, "kl_free_bits")
+    if tc_weight is not None:
+        tcw = number(tc_weight, "tc_weight")
+        if fb > 0.0 or capacity is not None:
+            raise ValueError("tc_weight, kl_free_bits and kl_capacity are alternatives: set one of them")
+        return _lib.KL_TC, tcw
     if capacity is None:
         return (_lib.KL_FREE_BITS, fb) if fb > 0.0 else (_lib.KL_PLAIN, 0.0)
     cap = number(capacity, "kl_capacity")
@@ -248,6 +273,7 @@ class VanillaVAE(nn.Module):
         max_batch: int | None = None,
         kl_free_bits: float = 0.0,
         kl_capacity: float | None = None,
+        tc_weight: float | None = None,
     ):
         super().__init__()
         if in_channels != 1:
@@ -271,9 +297,10 @@ class VanillaVAE(nn.Module):
         self.compute_dtype = compute_dtype
         _recon_kind(recon_loss)
         self.recon_loss = recon_loss
-        _kl_objective(kl_free_bits, kl_capacity)
+        _kl_objective(kl_free_bits, kl_capacity, tc_weight)
         self.kl_free_bits = kl_free_bits
         self.kl_capacity = kl_capacity
+        self.tc_weight = tc_weight
         s = self.img_size // 16 if self.generalised else 2
         self.last_conv_size = s * s  # models.py:33 hard-wires 4
         self.flattened_size = self.last_conv_size * hidden_dims[-1]
@@ -444,8 +471,9 @@ class VanillaVAE(nn.Module):
                     self._init_library_comm()
             self._max_batch = need
         self._ctx.set_recon(_recon_kind(self.recon_loss))
-        if self.kl_capacity is not None or self.kl_free_bits != 0.0 or self._ctx.kl[0] != _lib.KL_PLAIN:
-            self._ctx.set_kl(_kl_objective(self.kl_free_bits, self.kl_capacity))
+        tcw = getattr(self, "tc_weight", None)
+        if self.kl_capacity is not None or self.kl_free_bits != 0.0 or tcw is not None or self._ctx.kl[0] != _lib.KL_PLAIN:
+            self._ctx.set_kl(_kl_objective(self.kl_free_bits, self.kl_capacity, tcw))
         return self._ctx
 
     # -- data parallel: the step library's own RCCL communicator (include/vae_step.h: vae_comm_*) ----------------------
@@ -805,6 +833,10 @@ class VanillaVAE(nn.Module):
                 _lib.check(_lib.lib().vae_loss(self._ctx.handle, float(self.kld_weight), out3.data_ptr(), self._stream()), "vae_loss")
             loss = out3[0].clone()
         else:
+            if getattr(self, "tc_weight", None) is not None:
+                raise ValueError("loss() on tensors that are not this model's last forward cannot take tc_weight: the total correlation "
+                                 "is evaluated at z = mu + eps * exp(log_var / 2) and only the model's own forward holds its eps "
+                                 "(pass the forward's own output, or use vae_total_correlation with the eps)")
             loss, out3 = _GenericELBO.apply(output["output"], output["input"], output["encoded"]["mu"],
                                             output["encoded"]["log_var"], self.kld_weight, _recon_kind(self.recon_loss),
                                             _kl_objective(self.kl_free_bits, self.kl_capacity))
@@ -821,6 +853,18 @@ class VanillaVAE(nn.Module):
         out = torch.empty(self.latent_dim, device=self._flat.device, dtype=torch.float64)
         with self._device_guard():
             _lib.check(_lib.lib().vae_kl_per_dim(self._ctx.handle, out.data_ptr(), self._stream()), "vae_kl_per_dim")
+        return out
+
+    def total_correlation(self) -> Tensor:
+        """Total correlation (nats) of the model's last forward / fused step / encode over the in-batch mixture, at that forward's own
+        z: a float64 device scalar with no host synchronisation.  With tc_weight set it is the very value the step's loss used;
+        otherwise it is computed on demand by the same kernels.  Data parallel: the replica's own batch."""
+        self._require_device()
+        if self._last is None or self._last["kind"] == "decode" or self._ctx is None:
+            raise RuntimeError("total_correlation needs a forward, fused step or encode of this model")
+        out = torch.empty((), device=self._flat.device, dtype=torch.float64)
+        with self._device_guard():
+            _lib.check(_lib.lib().vae_last_total_correlation(self._ctx.handle, out.data_ptr(), self._stream()), "vae_last_total_correlation")
         return out
 
     def sample(self, num_samples: int, current_device: int, **kwargs) -> Tensor:

@@ -297,11 +297,13 @@ def train_one_epoch(config, model, optimizer, scheduler, criterion, dataloader, 
     torch_clip = max_grad_norm is not None and not isinstance(optimizer, FusedAdamW)
     fused_clip = isinstance(optimizer, FusedAdamW) and optimizer._clip_on
     grad_norm = None
-    # KL control (optional config fields; none of them: exactly the loop without it): free bits go to the model once, the weight
+    # KL control (optional config fields; none of them: exactly the loop without it): free bits and the TC weight go to the model once, the weight
     # and the capacity are host numbers set before each step - every step entry point takes them per call, nothing synchronises
     kl_schedule = KLSchedule.from_config(config, model)
     if getattr(config, "kl_free_bits", None) is not None:
         model.kl_free_bits = config.kl_free_bits
+    if getattr(config, "kl_tc_weight", None) is not None:
+        model.tc_weight = config.kl_tc_weight
     n_batches = len(dataloader)
     in_flight = deque()   # pinned host batches a device kernel may still be reading, with the event that follows that kernel
     for batch_idx, (stimuli, y_true) in enumerate(dataloader):
