@@ -1,8 +1,5 @@
 """Differentiable encode / decode / eval-mode forwards and x.grad on the GPU (vae_encode, vae_decode, vae_backward_ex).
 Yardstick: torch f64 autograd on the CPU, on the same state dict (perturbed BatchNorm affine values and running statistics)."""
-import ctypes
-import json
-
 import numpy as np
 import pytest
 import torch
@@ -11,7 +8,7 @@ import torch.nn.functional as F
 from oracle import vae_oracle as vo
 from tests.test_loglik_gpu import model_for
 from tests.path_local import LOSS_SCALE, upstream_weights
-from tests.util import PRE_BN_BIAS, rel_l2
+from tests.util import PRE_BN_BIAS, profile_sequence, rel_l2
 
 pytestmark = pytest.mark.gpu
 
@@ -83,18 +80,6 @@ def inputs(B, H, L, seed):
     x = torch.from_numpy(vo.synth_pianoroll(B, H, seed))
     eps = torch.from_numpy(vo.counter_normal(B * L, seed, 5).reshape(B, L)).float()
     return x, eps
-
-
-def profile_sequence(model, fn):
-    L_ = __import__("torch_vae_amd._lib", fromlist=["lib"]).lib()
-    h = model._ctx.handle
-    L_.vae_profile(h, 1)
-    fn()
-    torch.cuda.synchronize()
-    buf = ctypes.create_string_buffer(1 << 18)
-    assert L_.vae_profile_sequence(h, buf, len(buf)) == 0
-    L_.vae_profile(h, 0)
-    return json.loads(buf.value.decode())
 
 
 DEC = ("decoder_input", "decoder", "final_layer")

@@ -6,16 +6,13 @@ over oracle.torch_cpu_step.TorchCpuStep.forward (tests/test_kl_control_host.py: 
 by the fixed rule there (choose_lambda), which also asserts that dimensions fall on both sides of it with a relative margin of at
 least 1e-2; C is 0.5 / 1.5 times the yardstick's KL, so both signs run.  Tolerances are the project's existing ones for the same
 comparisons (tests/test_recon_loss_gpu.py, tests/test_parity_gpu.py)."""
-import ctypes
-import json
-
 import numpy as np
 import pytest
 import torch
 
 from oracle import vae_oracle as vo
 from tests.test_kl_control_host import (KlCpuStep, check_lambda, choose_lambda, cpu_kl_step, kl_terms, shaped_term, synth_inputs)
-from tests.util import PRE_BN_BIAS, flat_grad_dict, make_model, perturbed_params, rel_l2
+from tests.util import PRE_BN_BIAS, flat_grad_dict, make_model, perturbed_params, profile_sequence, rel_l2
 
 pytestmark = pytest.mark.gpu
 GRAD_TOL_F32 = 5e-3          # tests/test_parity_gpu.py GRAD_TOL["f32"] (LeakyReLU kink ties)
@@ -396,18 +393,6 @@ def test_reduction_is_reproducible_and_matches_latent_statistics(H, L, B, gen):
 
 
 # ---- 10. the default path launches what it did -----------------------------------------------------------------------------
-def profile_sequence(model, fn):
-    L_ = __import__("torch_vae_amd._lib", fromlist=["lib"]).lib()
-    h = model._ctx.handle
-    L_.vae_profile(h, 1)
-    fn()
-    torch.cuda.synchronize()
-    buf = ctypes.create_string_buffer(1 << 18)
-    assert L_.vae_profile_sequence(h, buf, len(buf)) == 0
-    L_.vae_profile(h, 0)
-    return json.loads(buf.value.decode())
-
-
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 def test_default_step_launches_nothing_new(dtype):
     from torch_vae_amd.optim import FusedAdamW

@@ -19,7 +19,7 @@ from oracle import vae_oracle as vo
 from tests.test_kl_control_host import synth_inputs
 from tests.test_tc_host import (GRAD_FLOOR, GRAD_REL, KERNEL_SHAPES, REGIMES, VALUE_ABS, VALUE_REL, TcCpuStep, assert_gate_not_vacuous,
                                 cpu_tc_step, kernel_case, tc_autograd)
-from tests.util import PRE_BN_BIAS, flat_grad_dict, make_model, perturbed_params, rel_l2
+from tests.util import PRE_BN_BIAS, flat_grad_dict, make_model, perturbed_params, profile_sequence, rel_l2
 
 pytestmark = pytest.mark.gpu
 GRAD_TOL_F32 = 5e-3          # tests/test_parity_gpu.py GRAD_TOL["f32"] (LeakyReLU kink ties)
@@ -276,7 +276,6 @@ def test_f32_train_one_epoch_with_tc_weight_against_cpu_loop():
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 def test_launch_sequence(dtype):
     """With the option off no launch is labelled tc_*; with it on, the sequence without the tc_* and kl_shape labels is the off one."""
-    from tests.test_kl_control_gpu import profile_sequence
     from torch_vae_amd import _lib
     from torch_vae_amd.optim import FusedAdamW
     H, L, B, gen = 64, 16, 5, True

@@ -1,4 +1,7 @@
 """Shared helpers for the parity tests."""
+import ctypes
+import json
+
 import numpy as np
 
 from oracle import vae_oracle as vo
@@ -77,3 +80,18 @@ def fetch_debug_tensor(model, which, shape, scale=1.0):
     _lib.check(_lib.lib().vae_debug_tensor(model._ctx.handle, which, t.data_ptr(), n, torch.cuda.current_stream().cuda_stream), "dbg")
     torch.cuda.synchronize()
     return t.cpu().numpy().reshape(shape).astype(np.float64) / scale
+
+
+def profile_sequence(model, fn):
+    """The launches of fn() in order, one entry per device launch (vae_profile_sequence), with profiling switched on around it."""
+    import torch
+    from torch_vae_amd import _lib
+    L_ = _lib.lib()
+    h = model._ctx.handle
+    L_.vae_profile(h, 1)
+    fn()
+    torch.cuda.synchronize()
+    buf = ctypes.create_string_buffer(1 << 18)
+    assert L_.vae_profile_sequence(h, buf, len(buf)) == 0
+    L_.vae_profile(h, 0)
+    return json.loads(buf.value.decode())

@@ -161,6 +161,8 @@ struct ProfScope {
         c->prof_recs.push_back(r); idx = (int)c->prof_recs.size() - 1;
     }
     ~ProfScope() { if (idx >= 0) (void)hipEventRecord(c->prof_recs[idx].e1, st); }
+    ProfScope(const ProfScope&) = delete;              // a copy would record the end event twice
+    ProfScope& operator=(const ProfScope&) = delete;
 };
 
 static inline size_t wgrad_slab_floats(const WgradKnobs& k, int B, int Hs, int Ws, int CA, int CB, int* nsplit_out, int* tps_out, int* WA_out, int* WB_out,

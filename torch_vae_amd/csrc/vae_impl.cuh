@@ -1,6 +1,7 @@
 // Launch sequencing of the VAE step, templated on the storage type T (bf16 / f16 / float).  Included by one
 // translation unit per storage type, which instantiates the entry points declared at the end of vae_ctx.h.
 #pragma once
+#include <type_traits>
 #include "vae_ctx.h"
 #include "conv_mfma.cuh"
 #include "conv_pipe.cuh"
@@ -15,19 +16,73 @@
 #include "grad_paths.cuh"
 
 // ---------------------------------------------------------------------------
-template <typename K> static int set_lds(K kernel, size_t bytes) {
-    if (bytes > 160 * 1024) return vae_set_error("lds", "tile needs more than 160 KiB LDS");
-    if (bytes > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+// Every kernel of this file starts here, so that the dynamic-LDS limit is raised before every launch that needs it (above
+// 48 KiB; nothing fits above 160 KiB) and the launch error is read after every launch (reported under `name`).  Nothing else.
+template <typename K, typename... Args>
+static int launch(const char* name, K kernel, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const Args&... args) {
+    if (lds_bytes > 160 * 1024) return vae_set_error("lds", "tile needs more than 160 KiB LDS");
+    if (lds_bytes > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (e != hipSuccess) return vae_set_error("hipFuncSetAttribute", hipGetErrorString(e));
     }
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, st, args...);
+    LAUNCH_CHECK(name);
     return 0;
 }
 
-template <typename T> static int launch_conv_pipe(vae_ctx* c, ConvArgs<T> a, bool is_down, hipStream_t st);
+// Run-time value -> template argument: returns f(std::integral_constant<int, V>{}) for the V of Vs... that equals v, an error
+// under `what` (the launch) when none does.  f is instantiated for every V listed and for no other, so a call site names exactly
+// the kernel variants that exist.
+template <int... Vs, typename F>
+static int pick_const(const char* what, int v, F&& f) {
+    int rc = 0;
+    const bool found = ((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
+    return found ? rc : vae_set_error(what, "no kernel variant for this value");
+}
+template <typename F> static int pick_bool(bool v, F&& f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
+// the reconstruction term the held forward ran with
+template <typename F> static int pick_recon(vae_ctx* c, F&& f) {
+    return c->fwd.recon == VAE_RECON_MSE ? f(std::integral_constant<int, VAE_RECON_MSE>{}) : f(std::integral_constant<int, VAE_RECON_BCE>{});
+}
+
+// Bands per image of a row-streaming launch.  Its units are (image, band of rows / bands rows); they run in rounds of one unit
+// per CU, and a unit takes rows / bands / rows_per_tick + fixed_ticks ticks (a band restages its halo rows: the fixed part).
+// So bands only where whole images would leave CUs idle or the last round mostly empty: the power of two up to max_bands, with
+// bands of at least min_rows rows, that needs the fewest ticks; the smallest of equals.
+static int stream_bands(int B, int rows, int max_bands, int min_rows, int rows_per_tick, int fixed_ticks) {
+    const int ncu = 256;
+    long best = -1; int nb = 1;
+    for (int cand = 1; cand <= max_bands && rows / cand >= min_rows; cand *= 2) {
+        const long rounds = ((long)B * cand + ncu - 1) / ncu, cost = rounds * (rows / cand / rows_per_tick + fixed_ticks);
+        if (best < 0 || cost < best) { best = cost; nb = cand; }
+    }
+    return nb;
+}
+
 // the pipelined kernels index their tensors with 32-bit byte offsets (and signed 32-bit element offsets)
 template <typename T> static bool fits_i32(const ConvArgs<T>& a) { return 4.0 * a.B * a.Hs * a.Ws * std::max(a.Cin, a.Cout) * sizeof(T) < 4294967296.0 && 4.0 * a.B * a.Hs * a.Ws * std::max(a.Cin, a.Cout) < 2147483648.0; }
+template <typename T> static bool will_pipe(vae_ctx* c, const ConvArgs<T>& a) { return c->use_pipelined && a.Cout <= c->knob_pipe_max_cout && fits_i32(a); }
+// can the weight gradient of BN layer i (2..5) run on materialised operands?  (16-bit storage, wide prefetching tile)
+template <typename T>
+static bool raw_wgrad_ok(vae_ctx* c, int i) {
+    return sizeof(T) == 2 && c->use_raw_wgrad && c->use_pipelined && c->wk.wide && c->wk.tile == 1 && !c->wk.force_simple && i >= 2 && i <= 5;
+}
 
+// tile organisation of a launch (ConvArgs / WgradArgs): log2 tile sizes, tile counts and their division magics
+template <typename A> static void apply_tiling(A& a, const Tiling& t) {
+    a.lth = t.lth; a.ltw = t.ltw; a.lTB = t.lTB; a.tiles_x = t.tiles_x; a.tiles_y = t.tiles_y;
+    a.m_tx = fastdiv_magic(t.tiles_x); a.m_txy = fastdiv_magic(t.tiles_x * t.tiles_y);
+}
+// Traffic / FLOP record of a 3x3 stride-2 layer launch, whichever kernel runs it.  A launch stages two sources exactly when bit 0
+// of a.two_src is set: only launch_conv_pipe ever sets bit 1 (knob_ablate_b, a diagnostic), so for the tiled kernels, which test
+// the whole word, the two readings agree.
+template <typename T> static ProfScope conv_prof(vae_ctx* c, const ConvArgs<T>& a, bool is_down, hipStream_t st) {
+    const double px_lo = (double)a.B * a.Hs * a.Ws, px_hi = 4 * px_lo;
+    const double px_in = is_down ? px_hi : px_lo, px_out = is_down ? px_lo : px_hi;
+    return ProfScope(c, is_down ? (a.epi == EPI_FWD ? "down_fwd(conv)" : "down_bwd(convT dgrad)") : (a.epi == EPI_FWD ? "up_fwd(convT)" : "up_bwd(conv dgrad)"),
+                     sizeof(T) * (px_in * a.Cin * ((a.two_src & 1) ? 2 : 1) + px_out * a.Cout * (a.epi == EPI_BWD ? 2 : 1) + 9.0 * a.Cin * a.Cout),
+                     2.0 * 9 * a.Cin * a.Cout * px_lo, st);
+}
 
 // Workgroup-specialised kernels of the deep layers (conv_deep.cuh): 16-bit storage, 128-pixel tiles of 8x16 pixels or two 8x8
 // images, 128 (down) / 64 (up) output channels per workgroup.  Returns 1 when the launch is outside their domain (the caller
@@ -45,8 +100,7 @@ static int launch_conv_deep(vae_ctx* c, ConvArgs<T> a, bool is_down, hipStream_t
         const int TB = 1 << t.lTB, th = 1 << t.lth, tw = 1 << t.ltw;
         if (!((tw == 16 && th == 8 && TB == 1) || (tw == 8 && th == 8 && TB == 2))) return 1;
         if ((a.two_src & 1) && a.slope != 1.f) return vae_set_error("conv_deep", "gradient operands are loaded without LeakyReLU (slope must be 1)");
-        a.lth = t.lth; a.ltw = t.ltw; a.lTB = t.lTB; a.tiles_x = t.tiles_x; a.tiles_y = t.tiles_y;
-        a.m_tx = fastdiv_magic(t.tiles_x); a.m_txy = fastdiv_magic(t.tiles_x * t.tiles_y);
+        apply_tiling(a, t);
         const int n_mt = ((a.B + TB - 1) / TB) * t.tiles_x * t.tiles_y, ntn = a.Cout / NCO, n_pairs = n_mt * ntn;
         a.n_mt = n_mt; a.rev = ((c->knob_rev >> 2) & 1) ? ((a.epi == EPI_FWD) ? ((c->knob_rev >> 4) & 1) : 1) : 0;
         DeepConvArgs<T> d; memset(&d, 0, sizeof(d));
@@ -66,115 +120,11 @@ static int launch_conv_deep(vae_ctx* c, ConvArgs<T> a, bool is_down, hipStream_t
         if (lds > 160 * 1024) return vae_set_error("conv_deep", "tile does not fit LDS");
         a.dbg = (c->dbg_buf && is_down == !(c->dbg_epi & 16) && c->tag && !strcmp(c->tag, c->dbg_tag) && a.epi == (c->dbg_epi & 15)) ? c->dbg_buf : nullptr;
         d.c = a; d.ablate = c->knob_ablate_f;
-        const double px_lo = (double)a.B * a.Hs * a.Ws, px_hi = 4 * px_lo;
-        const double px_in = is_down ? px_hi : px_lo, px_out = is_down ? px_lo : px_hi;
-        ProfScope ps(c, is_down ? (a.epi == EPI_FWD ? "down_fwd(conv)" : "down_bwd(convT dgrad)") : (a.epi == EPI_FWD ? "up_fwd(convT)" : "up_bwd(conv dgrad)"),
-                     sizeof(T) * (px_in * a.Cin * ((a.two_src & 1) ? 2 : 1) + px_out * a.Cout * (a.epi == EPI_BWD ? 2 : 1) + 9.0 * a.Cin * a.Cout),
-                     2.0 * 9 * a.Cin * a.Cout * px_lo, st);
-#define DEEP_CASE(K, E) { if (set_lds(K<T, E>, lds)) return -1; hipLaunchKernelGGL((K<T, E>), dim3(grid), dim3(512), lds, st, d, n_pairs, ntn); }
-        if (is_down) { if (a.epi == EPI_FWD) DEEP_CASE(dn3_kernel, EPI_FWD) else if (a.epi == EPI_BWD) DEEP_CASE(dn3_kernel, EPI_BWD) else DEEP_CASE(dn3_kernel, EPI_PLAIN) }
-        else { if (a.epi == EPI_FWD) DEEP_CASE(up3_kernel, EPI_FWD) else DEEP_CASE(up3_kernel, EPI_BWD) }
-#undef DEEP_CASE
-        LAUNCH_CHECK("conv_deep_kernel");
-        return 0;
+        ProfScope ps = conv_prof(c, a, is_down, st);
+        const auto go = [&](auto kernel) { return launch("conv_deep_kernel", kernel, dim3(grid), dim3(512), lds, st, d, n_pairs, ntn); };
+        if (is_down) return pick_const<EPI_FWD, EPI_BWD, EPI_PLAIN>("conv_deep", a.epi, [&](auto E) { return go(dn3_kernel<T, decltype(E)::value>); });
+        return pick_const<EPI_FWD, EPI_BWD>("conv_deep", a.epi, [&](auto E) { return go(up3_kernel<T, decltype(E)::value>); });
     }
-}
-
-template <typename T>
-static int launch_down(vae_ctx* c, ConvArgs<T> a, hipStream_t st) {
-    if constexpr (sizeof(T) == 2) {
-        // encoder.1's forward on 128x128 images: the row-streaming kernel (dnfirst_stream.cuh)
-        if (c->use_dnf_stream && a.epi == EPI_FWD && a.Cin == 32 && a.Cout == 64 && a.Hs == dfs::HO && a.Ws == dfs::WO && !a.stage_out && !a.two_src) {
-            DnFirstStreamArgs<T> m;
-            m.yin = a.src0; m.coef = a.coef; m.slope = a.slope; m.fuse = a.fuse; m.wp = a.wp; m.bias = a.bias; m.out = a.out; m.stat = a.stat; m.B = a.B;
-            const int ncu = 256;
-            long best = -1; int nb = 1;
-            for (int cand = 1; cand <= 8 && dfs::HO / cand >= 4; cand *= 2) {
-                const long rounds = ((long)a.B * cand + ncu - 1) / ncu, cost = rounds * (dfs::HO / cand / 2 + 2);
-                if (best < 0 || cost < best) { best = cost; nb = cand; }
-            }
-            m.nb = nb; m.RB = dfs::HO / nb; m.n_units = a.B * nb;
-            const double px_out = (double)a.B * a.Hs * a.Ws;
-            ProfScope ps(c, "down_fwd(conv)", sizeof(T) * (4 * px_out * 32 + px_out * 64 + 9.0 * 32 * 64), 2.0 * 9 * 32 * 64 * px_out, st);
-            const size_t lds = dnfirst_stream_lds();
-            if (set_lds(dnfirst_stream_kernel<T>, lds)) return -1;
-            hipLaunchKernelGGL((dnfirst_stream_kernel<T>), dim3(std::min(m.n_units, ncu)), dim3(768), lds, st, m);
-            LAUNCH_CHECK("dnfirst_stream_kernel");
-            return 0;
-        }
-    }
-    if (c->use_pipelined) { const int rc = launch_conv_deep<T>(c, a, true, st); if (rc <= 0) return rc; }
-    if (c->use_pipelined && a.Cout <= c->knob_pipe_max_cout && fits_i32(a)) return launch_conv_pipe<T>(c, a, true, st);
-    Tiling t = make_tiling(a.Hs, a.Ws, 128);
-    a.lth = t.lth; a.ltw = t.ltw; a.lTB = t.lTB; a.tiles_x = t.tiles_x; a.tiles_y = t.tiles_y;
-    const int TB = 1 << t.lTB, th = 1 << t.lth, tw = 1 << t.ltw;
-    const int n_tiles = ((a.B + TB - 1) / TB) * t.tiles_x * t.tiles_y;
-    a.m_pp = fastdiv_magic((2 * th + 1) * (2 * tw + 1)); a.m_pw = fastdiv_magic(2 * tw + 1); a.m_tx = fastdiv_magic(t.tiles_x); a.m_txy = fastdiv_magic(t.tiles_x * t.tiles_y);
-    const int NT = std::min(4, a.Cout / 32);
-    const size_t lds = ((3 * a.Cin * 4 + 15) & ~15) + (size_t)TB * (2 * th + 1) * (2 * tw + 1) * PATCH_PITCH + 4 * NT * 32 * 2 * 4;
-    dim3 grid(n_tiles, a.Cout / (32 * NT));
-    const double px_out = (double)a.B * a.Hs * a.Ws, px_in = 4 * px_out;
-    ProfScope ps(c, a.epi == EPI_FWD ? "down_fwd(conv)" : "down_bwd(convT dgrad)",
-                 sizeof(T) * (px_in * a.Cin * (a.two_src ? 2 : 1) + px_out * a.Cout * (a.epi == EPI_BWD ? 2 : 1) + 9.0 * a.Cin * a.Cout),
-                 2.0 * 9 * a.Cin * a.Cout * px_out, st);
-#define DOWN_CASE(N) { if (set_lds(down_kernel<T, N>, lds)) return -1; hipLaunchKernelGGL((down_kernel<T, N>), grid, dim3(256), lds, st, a); }
-    if (NT == 1) DOWN_CASE(1) else if (NT == 2) DOWN_CASE(2) else DOWN_CASE(4)
-#undef DOWN_CASE
-    LAUNCH_CHECK("down_kernel");
-    return 0;
-}
-
-template <typename T>
-static int launch_up(vae_ctx* c, ConvArgs<T> a, hipStream_t st) {
-    if constexpr (sizeof(T) == 2) {
-        // final_layer.0's forward on 128x128 images: the row-streaming kernel (upfinal_stream.cuh)
-        const bool upf7 = a.Cin == 32 && a.Hs == 64 && a.Ws == 64, upf6 = a.Cin == 64 && a.Hs == 32 && a.Ws == 32;   // final_layer.0 / decoder.2 at 128x128
-        // (decoder.2 - bit 1 of the option - measures the same 32 us as the tiled kernel: off by default)
-        if (a.epi == EPI_FWD && a.Cout == 32 && ((upf7 && (c->use_upf_stream & 1)) || (upf6 && (c->use_upf_stream & 2))) && !a.stage_out && !a.two_src) {
-            const int HLr = a.Hs;
-            UpFinalStreamArgs<T> m;
-            m.yin = a.src0; m.coef = a.coef; m.slope = a.slope; m.fuse = a.fuse; m.wp = a.wp; m.bias = a.bias; m.out = a.out; m.stat = a.stat; m.B = a.B;
-            const int ncu = 256;
-            long best = -1; int nb = 1;
-            for (int cand = 1; cand <= 8 && HLr / cand >= 8; cand *= 2) {
-                const long rounds = ((long)a.B * cand + ncu - 1) / ncu, cost = rounds * (HLr / cand / 4 + 2);
-                if (best < 0 || cost < best) { best = cost; nb = cand; }
-            }
-            m.nb = nb; m.RB = HLr / nb; m.n_units = a.B * nb;
-            const double px_in = (double)a.B * a.Hs * a.Ws;
-            ProfScope ps(c, "up_fwd(convT)", sizeof(T) * (px_in * a.Cin + 4 * px_in * 32 + 9.0 * a.Cin * 32), 2.0 * 9 * a.Cin * 32 * px_in, st);
-            if (upf7) {
-                const size_t lds = upfinal_stream_lds<32, 64>();
-                if (set_lds(upfinal_stream_kernel<T, 32, 64>, lds)) return -1;
-                hipLaunchKernelGGL((upfinal_stream_kernel<T, 32, 64>), dim3(std::min(m.n_units, ncu)), dim3(1024), lds, st, m);
-            } else {
-                const size_t lds = upfinal_stream_lds<64, 32>();
-                if (set_lds(upfinal_stream_kernel<T, 64, 32>, lds)) return -1;
-                hipLaunchKernelGGL((upfinal_stream_kernel<T, 64, 32>), dim3(std::min(m.n_units, ncu)), dim3(1024), lds, st, m);
-            }
-            LAUNCH_CHECK("upfinal_stream_kernel");
-            return 0;
-        }
-    }
-    if (c->use_pipelined) { const int rc = launch_conv_deep<T>(c, a, false, st); if (rc <= 0) return rc; }
-    if (c->use_pipelined && a.Cout <= c->knob_pipe_max_cout && fits_i32(a)) return launch_conv_pipe<T>(c, a, false, st);
-    Tiling t = make_tiling(a.Hs, a.Ws, 128);
-    a.lth = t.lth; a.ltw = t.ltw; a.lTB = t.lTB; a.tiles_x = t.tiles_x; a.tiles_y = t.tiles_y;
-    const int TB = 1 << t.lTB, th = 1 << t.lth, tw = 1 << t.ltw;
-    const int n_tiles = ((a.B + TB - 1) / TB) * t.tiles_x * t.tiles_y;
-    a.m_pp = fastdiv_magic((th + 1) * (tw + 1)); a.m_pw = fastdiv_magic(tw + 1); a.m_tx = fastdiv_magic(t.tiles_x); a.m_txy = fastdiv_magic(t.tiles_x * t.tiles_y);
-    const int NT = std::min(2, a.Cout / 32);
-    const size_t lds = ((3 * a.Cin * 4 + 15) & ~15) + (size_t)TB * (th + 1) * (tw + 1) * PATCH_PITCH + 4 * NT * 32 * 2 * 4;
-    dim3 grid(n_tiles, a.Cout / (32 * NT));
-    const double px_in = (double)a.B * a.Hs * a.Ws, px_out = 4 * px_in;
-    ProfScope ps(c, a.epi == EPI_FWD ? "up_fwd(convT)" : "up_bwd(conv dgrad)",
-                 sizeof(T) * (px_in * a.Cin * (a.two_src ? 2 : 1) + px_out * a.Cout * (a.epi == EPI_BWD ? 2 : 1) + 9.0 * a.Cin * a.Cout),
-                 2.0 * 9 * a.Cin * a.Cout * px_in, st);
-#define UP_CASE(N) { if (set_lds(up_kernel<T, N>, lds)) return -1; hipLaunchKernelGGL((up_kernel<T, N>), grid, dim3(256), lds, st, a); }
-    if (NT == 1) UP_CASE(1) else UP_CASE(2)
-#undef UP_CASE
-    LAUNCH_CHECK("up_kernel");
-    return 0;
 }
 
 // persistent, prefetched variants (conv_pipe.cuh)
@@ -195,12 +145,11 @@ static int launch_conv_pipe(vae_ctx* c, ConvArgs<T> a, bool is_down, hipStream_t
     const bool lay42 = lay22 && NT == 2 && sizeof(T) == 2 && c->knob_down_waves == 8 && (c->knob_lay42 != 0);   // eight waves: 4 x 2 grid
     const bool wv = sizeof(T) == 2 && !lay22 && NT <= c->knob_wave_nt_max;
     Tiling t = make_tiling(a.Hs, a.Ws, wv ? 32 : 128);
-    a.lth = t.lth; a.ltw = t.ltw; a.lTB = t.lTB; a.tiles_x = t.tiles_x; a.tiles_y = t.tiles_y;
+    apply_tiling(a, t);
     const int TB = 1 << t.lTB, th = 1 << t.lth, tw = 1 << t.ltw;
     const int n_mt = ((a.B + TB - 1) / TB) * t.tiles_x * t.tiles_y;
     const int PHW = is_down ? (2 * th + 1) * (2 * tw + 1) : (th + 1) * (tw + 1);
     a.m_pp = fastdiv_magic(PHW); a.m_pw = fastdiv_magic(is_down ? 2 * tw + 1 : tw + 1);
-    a.m_tx = fastdiv_magic(t.tiles_x); a.m_txy = fastdiv_magic(t.tiles_x * t.tiles_y);
     const int ntn = a.Cout / (32 * NT), n_pairs = n_mt * ntn;
     a.n_mt = n_mt; a.rev = ((c->knob_rev >> 2) & 1) ? ((a.epi == EPI_FWD) ? ((c->knob_rev >> 4) & 1) : 1) : 0;   // bit 2: backward launches, bit 4: forward too
     if (c->knob_rev & 32) { a.rev = c->fwd.walk_dir; c->fwd.walk_dir ^= 1; }   // bit 5: alternate the direction launch by launch
@@ -216,40 +165,98 @@ static int launch_conv_pipe(vae_ctx* c, ConvArgs<T> a, bool is_down, hipStream_t
     int grid = std::min(n_wg_pairs, 256 * ((c->knob_bwd_per_cu > 0 && a.epi != EPI_FWD) ? std::min(per_cu, c->knob_bwd_per_cu) : per_cu));
     grid = std::max(ntn, grid / ntn * ntn);   // a workgroup must stay on one N tile (register-resident statistics)
     a.xcd = (c->knob_xcd_map && grid % 8 == 0 && (grid / 8) % ntn == 0) ? grid / 8 : 0;   // contiguous id range per XCD (conv_pipe.cuh: vb)
-    const double px_lo = (double)a.B * a.Hs * a.Ws, px_hi = 4 * px_lo;
-    const double px_in = is_down ? px_hi : px_lo, px_out = is_down ? px_lo : px_hi;
-    ProfScope ps(c, is_down ? (a.epi == EPI_FWD ? "down_fwd(conv)" : "down_bwd(convT dgrad)") : (a.epi == EPI_FWD ? "up_fwd(convT)" : "up_bwd(conv dgrad)"),
-                 sizeof(T) * (px_in * a.Cin * ((a.two_src & 1) ? 2 : 1) + px_out * a.Cout * (a.epi == EPI_BWD ? 2 : 1) + 9.0 * a.Cin * a.Cout),
-                 2.0 * 9 * a.Cin * a.Cout * px_lo, st);
+    ProfScope ps = conv_prof(c, a, is_down, st);
     if (((a.two_src & 1) != 0) != (a.epi != EPI_FWD)) return vae_set_error("conv_pipe", "forward launches stage one source, backward launches two");
-#define PIPE_CASE(K, N, E, V) { if (set_lds(K<T, N, E, V>, lds)) return -1; hipLaunchKernelGGL((K<T, N, E, V>), dim3(grid), dim3(256), lds, st, a, n_pairs, ntn); }
-#define PIPE_CASE22(N, E) { if (set_lds(down2_kernel<T, N, E, false, 1>, lds)) return -1; hipLaunchKernelGGL((down2_kernel<T, N, E, false, 1>), dim3(grid), dim3(256), lds, st, a, n_pairs, ntn); }
-#define PIPE_CASE42(E) { if (set_lds(down2_kernel<T, 2, E, false, 3>, lds)) return -1; hipLaunchKernelGGL((down2_kernel<T, 2, E, false, 3>), dim3(grid), dim3(512), lds, st, a, n_pairs, ntn); }
-#define PIPE_CASE24(E) { if (set_lds(down2_kernel<T, 4, E, false, 2>, lds)) return -1; hipLaunchKernelGGL((down2_kernel<T, 4, E, false, 2>), dim3(grid), dim3(512), lds, st, a, n_pairs, ntn); }
-#define PIPE_WV(K, N, E) { if constexpr (sizeof(T) == 2) { if (wv) PIPE_CASE(K, N, E, true) else PIPE_CASE(K, N, E, false) } else PIPE_CASE(K, N, E, false) }
-#define PIPE_EPI(K, N) { if (a.epi == EPI_FWD) PIPE_WV(K, N, EPI_FWD) else if (a.epi == EPI_BWD) PIPE_WV(K, N, EPI_BWD) else PIPE_WV(K, N, EPI_PLAIN) }
-#define PIPE_EPI22(N) { if (a.epi == EPI_FWD) PIPE_CASE22(N, EPI_FWD) else if (a.epi == EPI_BWD) PIPE_CASE22(N, EPI_BWD) else PIPE_CASE22(N, EPI_PLAIN) }
-    if (lay24) { if constexpr (sizeof(T) == 2) { if (a.epi == EPI_FWD) PIPE_CASE24(EPI_FWD) else if (a.epi == EPI_BWD) PIPE_CASE24(EPI_BWD) else PIPE_CASE24(EPI_PLAIN) } }
-    else if (lay42) { if constexpr (sizeof(T) == 2) { if (a.epi == EPI_FWD) PIPE_CASE42(EPI_FWD) else if (a.epi == EPI_BWD) PIPE_CASE42(EPI_BWD) else PIPE_CASE42(EPI_PLAIN) } }
-    else if (lay22) { if (NT == 2) PIPE_EPI22(2) else { if constexpr (sizeof(T) == 2) PIPE_EPI22(4) } }
-    else if (is_down) { if (NT == 1) PIPE_EPI(down2_kernel, 1) else if (NT == 2) PIPE_EPI(down2_kernel, 2) else PIPE_EPI(down2_kernel, 4) }
-    else if (a.epi == EPI_FWD) { if (NT == 1) PIPE_WV(up2_kernel, 1, EPI_FWD) else PIPE_WV(up2_kernel, 2, EPI_FWD) }
-    else if (a.epi == EPI_BWD) PIPE_WV(up2_kernel, 1, EPI_BWD)
-    else return vae_set_error("conv_pipe", "up kernel has no plain epilogue");
-#undef PIPE_EPI22
-#undef PIPE_EPI
-#undef PIPE_WV
-#undef PIPE_CASE42
-#undef PIPE_CASE24
-#undef PIPE_CASE22
-#undef PIPE_CASE
-    LAUNCH_CHECK("conv_pipe_kernel");
-    return 0;
+    // the variant: template arguments <T, NT, epilogue, wave-independent tiles[, wave grid of the wide down tiles: 1 2x2, 2 2x4, 3 4x2]>
+    const auto go = [&](auto kernel, int threads) { return launch("conv_pipe_kernel", kernel, dim3(grid), dim3(threads), lds, st, a, n_pairs, ntn); };
+    const auto epi = [&](auto f) { return pick_const<EPI_FWD, EPI_BWD, EPI_PLAIN>("conv_pipe", a.epi, f); };
+    const auto wave = [&](auto f) {   // wave-independent tiles exist for 16-bit storage only
+        if constexpr (sizeof(T) == 2) { if (wv) return f(std::true_type{}); }
+        return f(std::false_type{});
+    };
+    if (lay24 || lay42 || (lay22 && NT == 4)) {   // eight waves or four channel blocks: 16-bit storage only
+        if constexpr (sizeof(T) == 2) {
+            if (lay24) return epi([&](auto E) { return go(down2_kernel<T, 4, decltype(E)::value, false, 2>, 512); });
+            if (lay42) return epi([&](auto E) { return go(down2_kernel<T, 2, decltype(E)::value, false, 3>, 512); });
+            return epi([&](auto E) { return go(down2_kernel<T, 4, decltype(E)::value, false, 1>, 256); });
+        }
+        return vae_set_error("conv_pipe", "wide down tiles need 16-bit storage");
+    }
+    if (lay22) return epi([&](auto E) { return go(down2_kernel<T, 2, decltype(E)::value, false, 1>, 256); });
+    if (is_down)
+        return pick_const<1, 2, 4>("conv_pipe", NT, [&](auto N) { return epi([&](auto E) { return wave([&](auto V) {
+            return go(down2_kernel<T, decltype(N)::value, decltype(E)::value, decltype(V)::value>, 256); }); }); });
+    if (a.epi == EPI_FWD)
+        return pick_const<1, 2>("conv_pipe", NT, [&](auto N) { return wave([&](auto V) { return go(up2_kernel<T, decltype(N)::value, EPI_FWD, decltype(V)::value>, 256); }); });
+    if (a.epi == EPI_BWD) return wave([&](auto V) { return go(up2_kernel<T, 1, EPI_BWD, decltype(V)::value>, 256); });
+    return vae_set_error("conv_pipe", "up kernel has no plain epilogue");
+}
+
+// The tiled kernels (conv_mfma.cuh): one 128-pixel tile per workgroup, no prefetch.  Whatever the kernels above do not take.
+template <typename T>
+static int launch_conv_tiled(vae_ctx* c, ConvArgs<T> a, bool is_down, hipStream_t st) {
+    Tiling t = make_tiling(a.Hs, a.Ws, 128);
+    apply_tiling(a, t);
+    const int TB = 1 << t.lTB, th = 1 << t.lth, tw = 1 << t.ltw;
+    const int n_tiles = ((a.B + TB - 1) / TB) * t.tiles_x * t.tiles_y;
+    const int PH = is_down ? 2 * th + 1 : th + 1, PW = is_down ? 2 * tw + 1 : tw + 1;   // staged input patch of a tile
+    a.m_pp = fastdiv_magic(PH * PW); a.m_pw = fastdiv_magic(PW);
+    const int NT = std::min(is_down ? 4 : 2, a.Cout / 32);
+    const size_t lds = ((3 * a.Cin * 4 + 15) & ~15) + (size_t)TB * PH * PW * PATCH_PITCH + 4 * NT * 32 * 2 * 4;
+    dim3 grid(n_tiles, a.Cout / (32 * NT));
+    ProfScope ps = conv_prof(c, a, is_down, st);
+    if (is_down) return pick_const<1, 2, 4>("down_kernel", NT, [&](auto N) { return launch("down_kernel", down_kernel<T, decltype(N)::value>, grid, dim3(256), lds, st, a); });
+    return pick_const<1, 2>("up_kernel", NT, [&](auto N) { return launch("up_kernel", up_kernel<T, decltype(N)::value>, grid, dim3(256), lds, st, a); });
+}
+
+// a layer launch outside the streaming special cases: the deep kernels, else the pipelined ones, else the tiled ones
+template <typename T>
+static int launch_conv(vae_ctx* c, const ConvArgs<T>& a, bool is_down, hipStream_t st) {
+    if (c->use_pipelined) { const int rc = launch_conv_deep<T>(c, a, is_down, st); if (rc <= 0) return rc; }
+    if (will_pipe(c, a)) return launch_conv_pipe<T>(c, a, is_down, st);
+    return launch_conv_tiled<T>(c, a, is_down, st);
+}
+
+template <typename T>
+static int launch_down(vae_ctx* c, ConvArgs<T> a, hipStream_t st) {
+    if constexpr (sizeof(T) == 2) {
+        // encoder.1's forward on 128x128 images: the row-streaming kernel (dnfirst_stream.cuh)
+        if (c->use_dnf_stream && a.epi == EPI_FWD && a.Cin == 32 && a.Cout == 64 && a.Hs == dfs::HO && a.Ws == dfs::WO && !a.stage_out && !a.two_src) {
+            DnFirstStreamArgs<T> m;
+            m.yin = a.src0; m.coef = a.coef; m.slope = a.slope; m.fuse = a.fuse; m.wp = a.wp; m.bias = a.bias; m.out = a.out; m.stat = a.stat; m.B = a.B;
+            m.nb = stream_bands(a.B, dfs::HO, 8, 4, 2, 2); m.RB = dfs::HO / m.nb; m.n_units = a.B * m.nb;
+            const double px_out = (double)a.B * a.Hs * a.Ws;
+            ProfScope ps(c, "down_fwd(conv)", sizeof(T) * (4 * px_out * 32 + px_out * 64 + 9.0 * 32 * 64), 2.0 * 9 * 32 * 64 * px_out, st);
+            return launch("dnfirst_stream_kernel", dnfirst_stream_kernel<T>, dim3(std::min(m.n_units, 256)), dim3(768), dnfirst_stream_lds(), st, m);
+        }
+    }
+    return launch_conv<T>(c, a, true, st);
+}
+
+template <typename T>
+static int launch_up(vae_ctx* c, ConvArgs<T> a, hipStream_t st) {
+    if constexpr (sizeof(T) == 2) {
+        // final_layer.0's forward on 128x128 images: the row-streaming kernel (upfinal_stream.cuh)
+        const bool upf7 = a.Cin == 32 && a.Hs == 64 && a.Ws == 64, upf6 = a.Cin == 64 && a.Hs == 32 && a.Ws == 32;   // final_layer.0 / decoder.2 at 128x128
+        // (decoder.2 - bit 1 of the option - measures the same 32 us as the tiled kernel: off by default)
+        if (a.epi == EPI_FWD && a.Cout == 32 && ((upf7 && (c->use_upf_stream & 1)) || (upf6 && (c->use_upf_stream & 2))) && !a.stage_out && !a.two_src) {
+            UpFinalStreamArgs<T> m;
+            m.yin = a.src0; m.coef = a.coef; m.slope = a.slope; m.fuse = a.fuse; m.wp = a.wp; m.bias = a.bias; m.out = a.out; m.stat = a.stat; m.B = a.B;
+            m.nb = stream_bands(a.B, a.Hs, 8, 8, 4, 2); m.RB = a.Hs / m.nb; m.n_units = a.B * m.nb;
+            const double px_in = (double)a.B * a.Hs * a.Ws;
+            ProfScope ps(c, "up_fwd(convT)", sizeof(T) * (px_in * a.Cin + 4 * px_in * 32 + 9.0 * a.Cin * 32), 2.0 * 9 * a.Cin * 32 * px_in, st);
+            const dim3 grid(std::min(m.n_units, 256));
+            if (upf7) return launch("upfinal_stream_kernel", upfinal_stream_kernel<T, 32, 64>, grid, dim3(1024), upfinal_stream_lds<32, 64>(), st, m);
+            return launch("upfinal_stream_kernel", upfinal_stream_kernel<T, 64, 32>, grid, dim3(1024), upfinal_stream_lds<64, 32>(), st, m);
+        }
+    }
+    return launch_conv<T>(c, a, false, st);
 }
 
 // (every caller reduces a parameter gradient: the result is written times c->fwd.ginv, the inverse of the f16 gradient scale)
 static int launch_reduce(const float* slab, int nslab, size_t n, float* out, int CA, int CB, hipStream_t st, vae_ctx* c) {
     ProfScope ps(c, "reduce_slab", 4.0 * n * (nslab + 1), 0, st);
+    const dim3 grid((unsigned)((n + 63) / 64));
     // many slabs of a small tensor (the output conv's 288 weights from 1536 workgroups): a handful of workgroups summing
     // them serially took 70-80 us; two levels: G partial sums per output, then the G partials
     if (nslab >= 256 && n * 32 * 4 <= c->reduce_tmp_floats) {
@@ -259,15 +266,10 @@ static int launch_reduce(const float* slab, int nslab, size_t n, float* out, int
         if (n * G > kSlot) return vae_set_error("reduce", "two-level scratch slot too small");
         float* tmp = c->reduce_tmp + (size_t)(c->reduce_slot++ % (c->reduce_tmp_floats / kSlot)) * kSlot;
         if (ps.idx >= 0) c->prof_recs[ps.idx].launches = 2;   // (vae_profile_sequence lists one entry per device launch)
-        hipLaunchKernelGGL(reduce_slab_kernel, dim3((unsigned)((n + 63) / 64), G), dim3(256), 0, st, slab, nslab, (int)n, tmp, 0, 0, 1.f, per);
-        LAUNCH_CHECK("reduce_slab_kernel");
-        hipLaunchKernelGGL(reduce_slab_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, tmp, G, (int)n, out, CA, CB, c->fwd.ginv, G);
-        LAUNCH_CHECK("reduce_slab_kernel");
-        return 0;
+        if (launch("reduce_slab_kernel", reduce_slab_kernel, dim3(grid.x, G), dim3(256), 0, st, slab, nslab, (int)n, tmp, 0, 0, 1.f, per)) return -1;
+        return launch("reduce_slab_kernel", reduce_slab_kernel, grid, dim3(256), 0, st, tmp, G, (int)n, out, CA, CB, c->fwd.ginv, G);
     }
-    hipLaunchKernelGGL(reduce_slab_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, slab, nslab, (int)n, out, CA, CB, c->fwd.ginv, nslab);
-    LAUNCH_CHECK("reduce_slab_kernel");
-    return 0;
+    return launch("reduce_slab_kernel", reduce_slab_kernel, grid, dim3(256), 0, st, slab, nslab, (int)n, out, CA, CB, c->fwd.ginv, nslab);
 }
 
 // raw: both operands are materialised tensors (a.s0 low-res side, a.g0 high-res side), staged as plain copies
@@ -290,11 +292,11 @@ static int launch_wgrad(vae_ctx* c, WgradArgs<T> a, float* dw_out, hipStream_t s
     const size_t need = wgrad_slab_floats(wk, a.B, a.Hs, a.Ws, a.CA, a.CB, &nsplit, &tps, &WA, &WB, pre, big);
     if (need > c->slab_floats) return vae_set_error("wgrad", "slab too small");
     Tiling t = make_tiling(a.Hs, a.Ws, WG_KP);
-    a.lth = t.lth; a.ltw = t.ltw; a.lTB = t.lTB; a.tiles_x = t.tiles_x; a.tiles_y = t.tiles_y;
+    apply_tiling(a, t);
     const int TB = 1 << t.lTB, th = 1 << t.lth, tw = 1 << t.ltw;
     a.n_tiles = ((a.B + TB - 1) / TB) * t.tiles_x * t.tiles_y; a.tiles_per_split = tps;
     a.slab = slab_buf; a.use_tr16 = c->use_tr16; a.rev = (c->knob_rev >> 3) & 1;
-    a.m_pp = fastdiv_magic((2 * th + 1) * (2 * tw + 1)); a.m_pw = fastdiv_magic(2 * tw + 1); a.m_tx = fastdiv_magic(t.tiles_x); a.m_txy = fastdiv_magic(t.tiles_x * t.tiles_y);
+    a.m_pp = fastdiv_magic((2 * th + 1) * (2 * tw + 1)); a.m_pw = fastdiv_magic(2 * tw + 1);
     const bool mid8 = c->wk.mid8 && WA == 2 && WB == 1 && pre;   // eight waves on the 64x32-channel tile
     const int nthr = (WA == 4 || mid8) ? 512 : 256, maxg = (5 * WB * 256 + nthr - 1) / nthr;
     const size_t lds = (size_t)(3 * 32 * WA + 3 * 32 * WB) * 4 + (size_t)WG_KP * (32 * WA * sizeof(T) + WG_SPAD) +
@@ -310,41 +312,34 @@ static int launch_wgrad(vae_ctx* c, WgradArgs<T> a, float* dw_out, hipStream_t s
     if (raw && !(WA == 4 && pre)) return vae_set_error("wgrad", "materialised operands: wide prefetching tile only");
     if (!raw && a.s_two == a.g_two) return vae_set_error("wgrad", "exactly one operand must be the gradient");
     const bool convt = a.g_two != 0;
-#define WG_CASE(A_, B_, C_, P_) { if (set_lds(wgrad_kernel<T, A_, B_, C_, P_>, lds)) return -1; hipLaunchKernelGGL((wgrad_kernel<T, A_, B_, C_, P_>), grid, dim3(256), lds, st, a); }
-#define WG_KIND(A_, B_, P_) { if (convt) WG_CASE(A_, B_, true, P_) else WG_CASE(A_, B_, false, P_) }
-    bool split_done = false;
-    if constexpr (sizeof(T) == 2) {
-        // producer / consumer form of the wide tile (wgrad_split.cuh): same results, staging and MFMA halves in different waves
-        const int npix = TB * (2 * th + 1) * (2 * tw + 1);
-        if (WA == 4 && pre && !raw && c->use_wgrad_split && c->use_tr16 && npix * (int)(32 * sizeof(T) / 16) <= wsp::MAXG * wsp::NP &&
-            wgrad_split_lds<T>(npix) <= 160 * 1024) {
-            a.dbg = (c->dbg_buf && c->tag && !strcmp(c->tag, c->dbg_tag) && c->dbg_epi == 32) ? c->dbg_buf : nullptr;   // (vae_debug_stamps(tag, 32, buf))
-            const size_t lds2 = wgrad_split_lds<T>(npix);
-            if (convt) { if (set_lds(wgrad_split_kernel<T, true>, lds2)) return -1; hipLaunchKernelGGL((wgrad_split_kernel<T, true>), grid, dim3(1024), lds2, st, a); }
-            else { if (set_lds(wgrad_split_kernel<T, false>, lds2)) return -1; hipLaunchKernelGGL((wgrad_split_kernel<T, false>), grid, dim3(1024), lds2, st, a); }
-            split_done = true;
-        }
-    }
-    if (split_done) {}
-    else if (WA == 4) {
+    // the variant: wgrad_kernel<T, WA, WB, ConvTranspose2d, prefetching[, waves, materialised operands]>
+    const auto go = [&](auto kernel, int threads, size_t bytes) { return launch("wgrad_kernel", kernel, grid, dim3(threads), bytes, st, a); };
+    int rc = 0;
+    if (WA == 4 || mid8) {   // eight waves: 16-bit storage only
         if constexpr (sizeof(T) == 2) {
-            if (raw) { if (set_lds(wgrad_kernel<T, 4, 1, false, true, 8, true>, lds)) return -1; hipLaunchKernelGGL((wgrad_kernel<T, 4, 1, false, true, 8, true>), grid, dim3(512), lds, st, a); }
-            else if (convt) { if (set_lds(wgrad_kernel<T, 4, 1, true, true, 8>, lds)) return -1; hipLaunchKernelGGL((wgrad_kernel<T, 4, 1, true, true, 8>), grid, dim3(512), lds, st, a); }
-            else { if (set_lds(wgrad_kernel<T, 4, 1, false, true, 8>, lds)) return -1; hipLaunchKernelGGL((wgrad_kernel<T, 4, 1, false, true, 8>), grid, dim3(512), lds, st, a); }
+            // producer / consumer form of the wide tile (wgrad_split.cuh): same results, staging and MFMA halves in different waves
+            const int npix = TB * (2 * th + 1) * (2 * tw + 1);
+            if (WA == 4 && pre && !raw && c->use_wgrad_split && c->use_tr16 && npix * (int)(32 * sizeof(T) / 16) <= wsp::MAXG * wsp::NP &&
+                wgrad_split_lds<T>(npix) <= 160 * 1024) {
+                a.dbg = (c->dbg_buf && c->tag && !strcmp(c->tag, c->dbg_tag) && c->dbg_epi == 32) ? c->dbg_buf : nullptr;   // (vae_debug_stamps(tag, 32, buf))
+                rc = pick_bool(convt, [&](auto C) { return go(wgrad_split_kernel<T, decltype(C)::value>, 1024, wgrad_split_lds<T>(npix)); });
+            }
+            else if (WA == 4 && raw) rc = go(wgrad_kernel<T, 4, 1, false, true, 8, true>, 512, lds);
+            else if (WA == 4) rc = pick_bool(convt, [&](auto C) { return go(wgrad_kernel<T, 4, 1, decltype(C)::value, true, 8>, 512, lds); });
+            else rc = pick_bool(convt, [&](auto C) { return go(wgrad_kernel<T, 2, 1, decltype(C)::value, true, 8>, 512, lds); });
         }
+        else rc = vae_set_error("wgrad", "eight-wave tiles need 16-bit storage");
     }
-    else if (mid8) {
-        if constexpr (sizeof(T) == 2) {
-            if (convt) { if (set_lds(wgrad_kernel<T, 2, 1, true, true, 8>, lds)) return -1; hipLaunchKernelGGL((wgrad_kernel<T, 2, 1, true, true, 8>), grid, dim3(512), lds, st, a); }
-            else { if (set_lds(wgrad_kernel<T, 2, 1, false, true, 8>, lds)) return -1; hipLaunchKernelGGL((wgrad_kernel<T, 2, 1, false, true, 8>), grid, dim3(512), lds, st, a); }
-        }
+    else {   // four waves, every storage type: the 64x64-, 64x32- and 32x32-channel tiles, prefetching or synchronous
+        const auto tile = [&](auto A, auto B_) { return pick_bool(convt, [&](auto C) { return pick_bool(pre, [&](auto P) {
+            return go(wgrad_kernel<T, decltype(A)::value, decltype(B_)::value, decltype(C)::value, decltype(P)::value>, 256, lds); }); }); };
+        using one = std::integral_constant<int, 1>; using two = std::integral_constant<int, 2>;
+        if (WA == 2 && WB == 2) rc = tile(two{}, two{});
+        else if (WA == 2 && WB == 1) rc = tile(two{}, one{});
+        else if (WA == 1 && WB == 1) rc = tile(one{}, one{});
+        else rc = vae_set_error("wgrad", "no kernel variant for this channel tile");
     }
-    else if (WA == 2 && WB == 2) { if (pre) WG_KIND(2, 2, true) else WG_KIND(2, 2, false) }
-    else if (WA == 2 && WB == 1) { if (pre) WG_KIND(2, 1, true) else WG_KIND(2, 1, false) }
-    else { if (pre) WG_KIND(1, 1, true) else WG_KIND(1, 1, false) }
-#undef WG_KIND
-#undef WG_CASE
-    LAUNCH_CHECK("wgrad_kernel");
+    if (rc) return -1;
     }
     return launch_reduce(slab_buf, nsplit, (size_t)9 * a.CA * a.CB, dw_out, a.CA, a.CB, st, c);
 }
@@ -361,13 +356,9 @@ static int launch_dense(vae_ctx* c, DenseArgs<T> a, int* nsplit_out, hipStream_t
     if ((size_t)nsplit * a.M * a.Npad > c->slab_floats) return vae_set_error("dense", "slab too small");
     a.slab = c->slab;
     dim3 grid(mt, nsplit, ntile);
-    ProfScope ps(c, "dense(fc / decoder_input dgrad)", sizeof(T) * ((double)a.M * a.K + (double)a.K * a.Npad), 2.0 * a.M * a.K * a.Npad, st);
-    if (NT == 1) hipLaunchKernelGGL((dense_kernel<T, 1>), grid, dim3(256), 0, st, a);
-    else if (NT == 2) hipLaunchKernelGGL((dense_kernel<T, 2>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((dense_kernel<T, 4>), grid, dim3(256), 0, st, a);
-    LAUNCH_CHECK("dense_kernel");
     *nsplit_out = nsplit;
-    return 0;
+    ProfScope ps(c, "dense(fc / decoder_input dgrad)", sizeof(T) * ((double)a.M * a.K + (double)a.K * a.Npad), 2.0 * a.M * a.K * a.Npad, st);
+    return pick_const<1, 2, 4>("dense_kernel", NT, [&](auto N) { return launch("dense_kernel", dense_kernel<T, decltype(N)::value>, grid, dim3(256), 0, st, a); });
 }
 // ---------------------------------------------------------------------------
 template <typename T>
@@ -392,9 +383,7 @@ int pack_weights(vae_ctx* c, const float* params, hipStream_t st) {
         c->packed_for = params;
     }
     ProfScope ps(c, "pack_weights", 0, 0, st);
-    hipLaunchKernelGGL((pack_kernel<T>), dim3((unsigned)c->knob_pack_grid, (unsigned)d.size()), dim3(256), 0, st, c->d_descs);
-    LAUNCH_CHECK("pack_kernel");
-    return 0;
+    return launch("pack_kernel", pack_kernel<T>, dim3((unsigned)c->knob_pack_grid, (unsigned)d.size()), dim3(256), 0, st, c->d_descs);
 }
 
 // ---- BatchNorm finalisation: folded into the consumer's prologue (BnFuse, common.cuh) or a standalone launch ----
@@ -418,20 +407,21 @@ static BnFuse make_fuse_bwd(vae_ctx* c, int i, const float* params, float* grads
 }
 static int bn_finalize_now(vae_ctx* c, const BnFuse& f, hipStream_t st) {
     ProfScope ps(c, f.mode == BNF_FWD ? "bn_fwd_finalize" : "bn_bwd_finalize", 0, 0, st);
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(1), dim3(256), 0, st, f);
-    LAUNCH_CHECK("bn_finalize_kernel");
-    return 0;
+    return launch("bn_finalize_kernel", bn_finalize_kernel, dim3(1), dim3(256), 0, st, f);
 }
-// Backward finalisation of a BN layer as its own launch; the consumers then read p0..p2 from the block (mode BNF_NONE).  After an
-// eval-mode forward always: BatchNorm on the running statistics (bn_eval_bwd_kernel, grad_paths.cuh).
-static int bn_bwd_standalone(vae_ctx* c, BnFuse& f, hipStream_t st) {
-    if (c->fwd.trained) { if (bn_finalize_now(c, f, st)) return -1; }
+// BatchNorm backward of layer i for the kernels that stage (dz_i, y_i) next.  After a train-mode forward, with use_fused_bn and
+// consumers that fold the finalisation into their prologue: the descriptor (mode BNF_BWD), nothing launched.  Otherwise the
+// finalisation is its own launch and the consumers read p0..p2 from the block (mode BNF_NONE); after an eval-mode forward always:
+// BatchNorm on the running statistics (bn_eval_bwd_kernel, grad_paths.cuh).
+static int bn_bwd_for(vae_ctx* c, int i, bool consumer_fuses, const float* params, float* grads, BnFuse* out, hipStream_t st) {
+    *out = make_fuse_bwd(c, i, params, grads);
+    if (consumer_fuses && c->use_fused_bn && c->fwd.trained) return 0;
+    if (c->fwd.trained) { if (bn_finalize_now(c, *out, st)) return -1; }
     else {
         ProfScope ps(c, "bn_eval_bwd_finalize", 0, 0, st);
-        hipLaunchKernelGGL(bn_eval_bwd_kernel, dim3(1), dim3(256), 0, st, f);
-        LAUNCH_CHECK("bn_eval_bwd_kernel");
+        if (launch("bn_eval_bwd_kernel", bn_eval_bwd_kernel, dim3(1), dim3(256), 0, st, *out)) return -1;
     }
-    f.mode = BNF_NONE;
+    out->mode = BNF_NONE;
     return 0;
 }
 // Coefficients of layer i for the kernel that stages its tensor next.  Train mode with a fusing consumer: returns
@@ -447,12 +437,19 @@ static int input_bn_fwd(vae_ctx* c, int i, const float* params, float* bn_runnin
         return bn_finalize_now(c, f, st);
     }
     if (!bn_running) return vae_set_error("vae_forward", "eval mode needs running statistics");
-    hipLaunchKernelGGL(bn_eval_coef_kernel, dim3(1), dim3(256), 0, st, params + c->poff[l.p_gamma], params + c->poff[l.p_beta],
-                       bn_running + c->bnoff[i], bn_running + c->bnoff[i] + l.C, l.block, l.C, kBnEps);
-    LAUNCH_CHECK("bn_eval_coef_kernel");
-    return 0;
+    return launch("bn_eval_coef_kernel", bn_eval_coef_kernel, dim3(1), dim3(256), 0, st, params + c->poff[l.p_gamma], params + c->poff[l.p_beta],
+                  bn_running + c->bnoff[i], bn_running + c->bnoff[i] + l.C, l.block, l.C, kBnEps);
 }
-template <typename T> static bool will_pipe(vae_ctx* c, const ConvArgs<T>& a) { return c->use_pipelined && a.Cout <= c->knob_pipe_max_cout && fits_i32(a); }
+
+// arguments of the output conv's forward MFMA kernel, from those of the plain kernel (per-sample mode included: a.part / a.tB)
+template <typename T>
+static ConvOutFwdMfmaArgs<T> convout_fwd_mfma_args(vae_ctx* c, const ConvOutArgs& a, const BnFuse& f7) {
+    ConvOutFwdMfmaArgs<T> m; memset(&m, 0, sizeof(m)); m.fuse = f7; m.rev = c->knob_rev & 1;
+    m.yf = reinterpret_cast<const T*>(a.yf); m.coef = a.coef; m.wt = a.wt; m.bias = a.bias; m.target = a.target;
+    m.xhat = a.xhat; m.dlogit = a.dlogit; m.accum = a.accum; m.B = a.B; m.H = a.H; m.W = a.W; m.n_tiles = a.B * (a.H / 8) * (a.W / 32);
+    m.inv_n = a.inv_n; m.slope = a.slope; m.part = a.part; m.tB = a.tB;
+    return m;
+}
 
 // Per-sample mode of the output conv (vae_log_likelihood sets c->ps_part / c->ps_tb around an eval-mode decode_impl): the
 // reconstruction term of every tile goes to c->ps_part (tile order: image, tile row, tile column; c->ps_ntile tiles per image),
@@ -460,29 +457,19 @@ template <typename T> static bool will_pipe(vae_ctx* c, const ConvArgs<T>& a) { 
 template <typename T>
 static int launch_convout_per_sample(vae_ctx* c, ConvOutArgs a, const BnFuse& f7, bool mfma_out, hipStream_t st) {
     const int B = a.B, H = a.H;
-    const bool mse = c->fwd.recon == VAE_RECON_MSE;
     a.part = c->ps_part; a.tB = c->ps_tb; a.xhat = nullptr; a.dlogit = nullptr; a.accum = nullptr;
     ProfScope ps(c, "convout_fwd_per_sample", ((double)sizeof(T) * 32 + 4.0) * B * H * H, 2.0 * 9 * 32 * B * H * H, st);
     if constexpr (sizeof(T) == 2) {
         if (mfma_out) {
-            ConvOutFwdMfmaArgs<T> m; memset(&m, 0, sizeof(m)); m.fuse = f7; m.rev = c->knob_rev & 1;
-            m.yf = reinterpret_cast<const T*>(c->lay[7].y); m.coef = a.coef; m.wt = a.wt; m.bias = a.bias; m.target = a.target;
-            m.B = B; m.H = H; m.W = H; m.n_tiles = B * (H / 8) * (H / 32); m.inv_n = a.inv_n; m.slope = kSlope;
-            m.part = a.part; m.tB = a.tB;
+            const ConvOutFwdMfmaArgs<T> m = convout_fwd_mfma_args<T>(c, a, f7);
             c->ps_ntile = (H / 8) * (H / 32);
             const dim3 grid(std::min(m.n_tiles, c->knob_convout_grid));
-            if (mse) hipLaunchKernelGGL((convout_fwd_mfma_kernel<T, VAE_RECON_MSE, true>), grid, dim3(256), 0, st, m);
-            else hipLaunchKernelGGL((convout_fwd_mfma_kernel<T, VAE_RECON_BCE, true>), grid, dim3(256), 0, st, m);
-            LAUNCH_CHECK("convout_fwd_mfma_kernel(per sample)");
-            return 0;
+            return pick_recon(c, [&](auto R) { return launch("convout_fwd_mfma_kernel(per sample)", convout_fwd_mfma_kernel<T, decltype(R)::value, true>, grid, dim3(256), 0, st, m); });
         }
     }
     c->ps_ntile = (H / 16) * (H / 32);
     const dim3 grid(B * (H / 16) * (H / 32));
-    if (mse) hipLaunchKernelGGL((convout_fwd_kernel<T, VAE_RECON_MSE, true>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((convout_fwd_kernel<T, VAE_RECON_BCE, true>), grid, dim3(256), 0, st, a);
-    LAUNCH_CHECK("convout_fwd_kernel(per sample)");
-    return 0;
+    return pick_recon(c, [&](auto R) { return launch("convout_fwd_kernel(per sample)", convout_fwd_kernel<T, decltype(R)::value, true>, grid, dim3(256), 0, st, a); });
 }
 
 // decoder half of the forward (models.py:147-175): decoder_input -> 3x ConvT blocks -> final_layer
@@ -496,22 +483,17 @@ int decode_impl(vae_ctx* c, const float* z, int B, const float* params, float* b
     const int H = c->H, L = c->L;
     c->tag = "latent";
     // decoder_input
-    if (c->use_latent_mfma & 1) {   // 64 feature columns x the whole batch per workgroup on the exact-f32 MFMA (latent_mfma.cuh)
-        RowGemmArgs g; memset(&g, 0, sizeof(g));
-        g.Y = z; g.ldy = L; g.K = L; g.Wf = params + c->poff[20]; g.bias = params + c->poff[21]; g.out = c->d0; g.B = B; g.F = (int)c->F; g.s2 = c->s2;
+    {
         ProfScope ps(c, "decin_fwd", (double)sizeof(T) * B * (double)c->F + 4.0 * c->F * L, 2.0 * B * c->F * L, st);
-        const size_t lds = row_gemm_lds<T>();
-        if (set_lds(row_gemm_kernel<T, 0>, lds)) return -1;
-        hipLaunchKernelGGL((row_gemm_kernel<T, 0>), dim3((unsigned)(c->F / 64)), dim3(256), lds, st, g);
-        LAUNCH_CHECK("row_gemm_kernel");
-    } else {
-        dim3 grid((unsigned)(c->F / 256), (B + 15) / 16);
-        ProfScope ps(c, "decin_fwd", (double)sizeof(T) * B * (double)c->F + 4.0 * c->F * L, 2.0 * B * c->F * L, st);
-        const size_t lds = decin_fwd_lds(L);
-        if (set_lds(decin_fwd_kernel<T>, lds)) return -1;
-        hipLaunchKernelGGL((decin_fwd_kernel<T>), grid, dim3(256), lds, st, z, params + c->poff[20], params + c->poff[21],
-                           reinterpret_cast<T*>(c->d0), B, (int)c->F, L, c->s2);
-        LAUNCH_CHECK("decin_fwd_kernel");
+        if (c->use_latent_mfma & 1) {   // 64 feature columns x the whole batch per workgroup on the exact-f32 MFMA (latent_mfma.cuh)
+            RowGemmArgs g; memset(&g, 0, sizeof(g));
+            g.Y = z; g.ldy = L; g.K = L; g.Wf = params + c->poff[20]; g.bias = params + c->poff[21]; g.out = c->d0; g.B = B; g.F = (int)c->F; g.s2 = c->s2;
+            if (launch("row_gemm_kernel", row_gemm_kernel<T, 0>, dim3((unsigned)(c->F / 64)), dim3(256), row_gemm_lds<T>(), st, g)) return -1;
+        } else {
+            dim3 grid((unsigned)(c->F / 256), (B + 15) / 16);
+            if (launch("decin_fwd_kernel", decin_fwd_kernel<T>, grid, dim3(256), decin_fwd_lds(L), st, z, params + c->poff[20], params + c->poff[21],
+                       reinterpret_cast<T*>(c->d0), B, (int)c->F, L, c->s2)) return -1;
+        }
     }
     for (int i = 4; i < 8; ++i) {
         c->tag = kLayerTag[i];
@@ -534,7 +516,7 @@ int decode_impl(vae_ctx* c, const float* z, int B, const float* params, float* b
         ConvOutArgs a;
         a.yf = c->lay[7].y; a.coef = c->lay[7].block; a.wt = c->wout_t; a.bias = params + c->poff[39]; a.target = x;
         a.xhat = xhat; a.dlogit = c->dlogit; a.accum = c->accum; a.B = B; a.H = H; a.W = H;
-        a.inv_n = (float)(1.0 / ((double)B * H * H)); a.slope = kSlope;
+        a.inv_n = (float)(1.0 / ((double)B * H * H)); a.slope = kSlope; a.part = nullptr; a.tB = 0;
         const bool mfma_out = sizeof(T) == 2 && c->use_mfma_convout && 64.0 * B * H * H < 4294967296.0;   // 32-bit byte offsets
         BnFuse f7;
         if (input_bn_fwd(c, 7, params, bn_running, nbt, train, mfma_out, &f7, st)) return -1;
@@ -546,28 +528,16 @@ int decode_impl(vae_ctx* c, const float* z, int B, const float* params, float* b
         c->fwd.dlogit_valid = 1;   // (begin_forward cleared both flags)
         if (c->ps_part) return launch_convout_per_sample<T>(c, a, f7, mfma_out, st);
         ProfScope ps(c, "convout_fwd+bce", ((double)sizeof(T) * 32 + 12.0) * B * H * H, 2.0 * 9 * 32 * B * H * H, st);
-        const bool mse = c->fwd.recon == VAE_RECON_MSE;
-        bool launched = false;
         if constexpr (sizeof(T) == 2) {
             if (mfma_out) {
-                ConvOutFwdMfmaArgs<T> m; m.fuse = f7; m.rev = c->knob_rev & 1;
-                m.yf = reinterpret_cast<const T*>(c->lay[7].y); m.coef = a.coef; m.wt = a.wt; m.bias = a.bias; m.target = x;
-                m.xhat = xhat; m.dlogit = c->dlogit; m.accum = c->accum; m.B = B; m.H = H; m.W = H; m.n_tiles = B * (H / 8) * (H / 32);
-                m.inv_n = a.inv_n; m.slope = kSlope;
+                const ConvOutFwdMfmaArgs<T> m = convout_fwd_mfma_args<T>(c, a, f7);
                 const dim3 grid(std::min(m.n_tiles, c->knob_convout_grid));
-                if (mse) hipLaunchKernelGGL((convout_fwd_mfma_kernel<T, VAE_RECON_MSE>), grid, dim3(256), 0, st, m);
-                else hipLaunchKernelGGL((convout_fwd_mfma_kernel<T, VAE_RECON_BCE>), grid, dim3(256), 0, st, m);
-                launched = true;
+                return pick_recon(c, [&](auto R) { return launch("convout_fwd_kernel", convout_fwd_mfma_kernel<T, decltype(R)::value>, grid, dim3(256), 0, st, m); });
             }
         }
-        if (!launched) {
-            const dim3 grid(B * (H / 16) * (H / 32));
-            if (mse) hipLaunchKernelGGL((convout_fwd_kernel<T, VAE_RECON_MSE>), grid, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((convout_fwd_kernel<T, VAE_RECON_BCE>), grid, dim3(256), 0, st, a);
-        }
-        LAUNCH_CHECK("convout_fwd_kernel");
+        const dim3 grid(B * (H / 16) * (H / 32));
+        return pick_recon(c, [&](auto R) { return launch("convout_fwd_kernel", convout_fwd_kernel<T, decltype(R)::value>, grid, dim3(256), 0, st, a); });
     }
-    return 0;
 }
 
 // encoder half of the forward (models.py:107-145, 177-183): encoder -> fc_mu | fc_var -> mu, log_var, z = eps * std + mu
@@ -575,16 +545,17 @@ template <typename T>
 int encode_impl(vae_ctx* c, const float* x, int B, const float* params, float* bn_running, int64_t* nbt,
                 const float* eps, uint64_t seed, int train, float* mu, float* lv, float* z, hipStream_t st) {
     const int H = c->H, L = c->L;
+    const auto draw_eps = [&](hipStream_t s) {
+        return launch("counter_normal_kernel", counter_normal_kernel, dim3((B * L + 255) / 256), dim3(256), 0, s, c->eps, (long)B * L, (unsigned long long)seed, 5ULL);
+    };
     // encoder block 0 (reads the raw f32 weights); the MFMA layers' packed weight images are built meanwhile
     c->tag = kLayerTag[0];
     {
         SideFork f = fork_side(c, st);
         if (f.rc) return f.rc;
         if (pack_weights<T>(c, params, f.st)) return -1;
-        if (!eps && (c->knob_lean & 1)) {   // the reparameterisation noise is input-independent: drawn beside the first conv, not in the latent chain
-            hipLaunchKernelGGL(counter_normal_kernel, dim3((B * L + 255) / 256), dim3(256), 0, f.st, c->eps, (long)B * L, (unsigned long long)seed, 5ULL);
-            LAUNCH_CHECK("counter_normal_kernel");
-        }
+        // the reparameterisation noise is input-independent: drawn beside the first conv, not in the latent chain
+        if (!eps && (c->knob_lean & 1) && draw_eps(f.st)) return -1;
         if (c->use_side_stream) HIP_CHECK_RET(hipEventRecord(c->ev_pack, f.st));
     }
     {
@@ -592,9 +563,8 @@ int encode_impl(vae_ctx* c, const float* x, int B, const float* params, float* b
         // a workgroup covers 64 quads of 4 output pixels per pass; few workgroups: one f64 atomic per channel each
         const int grid = (int)std::min<long>((P / 4 + 63) / 64, c->knob_conv1_grid);
         ProfScope ps(c, "conv1_fwd", 4.0 * B * H * H + (double)sizeof(T) * 32.0 * P, 2.0 * 9 * 32 * P, st);
-        hipLaunchKernelGGL((conv1_fwd_kernel<T>), dim3(grid), dim3(256), 0, st, x, params + c->poff[0], params + c->poff[1],
-                           reinterpret_cast<T*>(c->lay[0].y), c->lay[0].stat_f, B, H, H);
-        LAUNCH_CHECK("conv1_fwd_kernel");
+        if (launch("conv1_fwd_kernel", conv1_fwd_kernel<T>, dim3(grid), dim3(256), 0, st, x, params + c->poff[0], params + c->poff[1],
+                   reinterpret_cast<T*>(c->lay[0].y), c->lay[0].stat_f, B, H, H)) return -1;
         if (c->use_side_stream) HIP_CHECK_RET(hipStreamWaitEvent(st, c->ev_pack, 0));
     }
     for (int i = 1; i < 4; ++i) {
@@ -621,17 +591,12 @@ int encode_impl(vae_ctx* c, const float* x, int B, const float* params, float* b
         int nsplit;
         if (launch_dense<T>(c, a, &nsplit, st)) return -1;
         if (eps) HIP_CHECK_RET(hipMemcpyAsync(c->eps, eps, (size_t)B * L * 4, hipMemcpyDeviceToDevice, st));
-        else if (!(c->knob_lean & 1)) {
-            hipLaunchKernelGGL(counter_normal_kernel, dim3((B * L + 255) / 256), dim3(256), 0, st, c->eps, (long)B * L, (unsigned long long)seed, 5ULL);
-            LAUNCH_CHECK("counter_normal_kernel");
-        }
+        else if (!(c->knob_lean & 1) && draw_eps(st)) return -1;
         LatentFwdArgs la;
         la.slab = c->slab; la.nslab = nsplit; la.npad = c->npad_fc; la.bmu = params + c->poff[17]; la.bvar = params + c->poff[19];
         la.eps = c->eps; la.mu = mu; la.lv = lv; la.z = z; la.accum = c->accum; la.B = B; la.L = L;
-        hipLaunchKernelGGL(latent_fwd_kernel, dim3((B * L * LAT_LANES + 255) / 256), dim3(256), 0, st, la);
-        LAUNCH_CHECK("latent_fwd_kernel");
+        return launch("latent_fwd_kernel", latent_fwd_kernel, dim3((B * L * LAT_LANES + 255) / 256), dim3(256), 0, st, la);
     }
-    return 0;
 }
 
 template <typename T>
@@ -672,8 +637,7 @@ static int launch_convt_fused(vae_ctx* c, int i, const float* params, float* gra
         const int fs = i == 7 ? 0 : 1;
         ConvTFusedArgs<T> a; memset(&a, 0, sizeof(a));
         a.dz = reinterpret_cast<const T*>(l.dz); a.y = reinterpret_cast<const T*>(l.y); a.gcoef = l.block + LC_P0 * l.C;
-        a.fuse = make_fuse_bwd(c, i, params, grads);
-        if (!c->use_fused_bn || !c->fwd.trained) { if (bn_bwd_standalone(c, a.fuse, st)) return -1; }   // standalone finalisation: coefficients from the block
+        if (bn_bwd_for(c, i, true, params, grads, &a.fuse, st)) return -1;
         a.wp = reinterpret_cast<const T*>(c->wp_dg[i]);
         a.yprev = reinterpret_cast<const T*>(lp.y); a.ocoef = lp.block; a.dzprev = reinterpret_cast<T*>(lp.dz); a.stat = lp.stat_b;
         a.slab = c->fused_slab[fs]; a.slope = kSlope;
@@ -688,16 +652,13 @@ static int launch_convt_fused(vae_ctx* c, int i, const float* params, float* gra
             ProfScope ps(c, recomp ? "convT_bwd_fused(dz recomputed+dgrad+wgrad)" : "convT_bwd_fused(dgrad+wgrad)",
                          sizeof(T) * ((recomp ? 1.0 : 2.0) * 4 * px * 32 + 2.0 * px * CLO + 9.0 * 32 * CLO) + 4.0 * 9 * 32 * CLO + (recomp ? 4.0 * 4 * px : 0.0),
                          2.0 * 2 * 9 * 32 * CLO * px + (recomp ? 2.0 * 9 * 32 * 4 * px : 0.0), st);
-            if (recomp) { if (set_lds(convt_bwd_fused_kernel<T, 32, true>, lds)) return -1; hipLaunchKernelGGL((convt_bwd_fused_kernel<T, 32, true>), dim3(grid), dim3(512), lds, st, a); }
-            else if (CLO == 32) { if (set_lds(convt_bwd_fused_kernel<T, 32>, lds)) return -1; hipLaunchKernelGGL((convt_bwd_fused_kernel<T, 32>), dim3(grid), dim3(512), lds, st, a); }
-            else { if (set_lds(convt_bwd_fused_kernel<T, 64>, lds)) return -1; hipLaunchKernelGGL((convt_bwd_fused_kernel<T, 64>), dim3(grid), dim3(512), lds, st, a); }
-            LAUNCH_CHECK("convt_bwd_fused_kernel");
+            const auto go = [&](auto kernel) { return launch("convt_bwd_fused_kernel", kernel, dim3(grid), dim3(512), lds, st, a); };
+            if (recomp ? go(convt_bwd_fused_kernel<T, 32, true>) : CLO == 32 ? go(convt_bwd_fused_kernel<T, 32>) : go(convt_bwd_fused_kernel<T, 64>)) return -1;
         }
         // the per-workgroup slabs are summed beside the chain (the buffer is this layer's own: next written in the next step)
         SideFork f = fork_side(c, st);
         if (f.rc) return -1;
-        if (launch_reduce(a.slab, grid, (size_t)9 * CLO * 32, grads + c->poff[l.p_convw], CLO, 32, f.st, c)) return -1;
-        return 0;
+        return launch_reduce(a.slab, grid, (size_t)9 * CLO * 32, grads + c->poff[l.p_convw], CLO, 32, f.st, c);
     }
 }
 
@@ -716,24 +677,19 @@ static int launch_conv_fused(vae_ctx* c, int i, const float* params, float* grad
         const int grid = std::min(a.n_tiles, c->knob_fused_grid);
         if ((size_t)grid * 9 * 64 * 32 > c->fused_slab_floats) return 1;
         a.dz = reinterpret_cast<const T*>(l.dz); a.y = reinterpret_cast<const T*>(l.y); a.gcoef = l.block + LC_P0 * l.C;
-        a.fuse = make_fuse_bwd(c, i, params, grads);
-        if (!c->use_fused_bn || !c->fwd.trained) { if (bn_bwd_standalone(c, a.fuse, st)) return -1; }
+        if (bn_bwd_for(c, i, true, params, grads, &a.fuse, st)) return -1;
         a.wp = reinterpret_cast<const T*>(c->wp_dg[i]);
         a.yprev = reinterpret_cast<const T*>(lp.y); a.ocoef = lp.block; a.dzprev = reinterpret_cast<T*>(lp.dz); a.stat = lp.stat_b;
         a.slab = c->fused_slab[2]; a.slope = kSlope; a.B = c->fwd.B; a.Hs = Hs; a.Ws = Ws; a.rev = (c->knob_rev >> 2) & 1; a.ablate = c->knob_ablate_f;
-        const size_t lds = conv_fused_lds();
         const double px = (double)c->fwd.B * Hs * Ws;
         {
             ProfScope ps(c, "conv_bwd_fused(dgrad+wgrad)", sizeof(T) * (2.0 * px * 64 + 2.0 * 4 * px * 32 + 9.0 * 32 * 64) + 4.0 * 9 * 32 * 64,
                          2.0 * 2 * 9 * 32 * 64 * px, st);
-            if (set_lds(conv_bwd_fused_kernel<T>, lds)) return -1;
-            hipLaunchKernelGGL((conv_bwd_fused_kernel<T>), dim3(grid), dim3(512), lds, st, a);
-            LAUNCH_CHECK("conv_bwd_fused_kernel");
+            if (launch("conv_bwd_fused_kernel", conv_bwd_fused_kernel<T>, dim3(grid), dim3(512), conv_fused_lds(), st, a)) return -1;
         }
         SideFork f = fork_side(c, st);
         if (f.rc) return -1;
-        if (launch_reduce(a.slab, grid, (size_t)9 * 64 * 32, grads + c->poff[l.p_convw], 64, 32, f.st, c)) return -1;
-        return 0;
+        return launch_reduce(a.slab, grid, (size_t)9 * 64 * 32, grads + c->poff[l.p_convw], 64, 32, f.st, c);
     }
 }
 
@@ -743,10 +699,54 @@ static int wgrad_on_side(vae_ctx* c, WgradArgs<T> w, float* dw_out, hipStream_t 
     if (f.rc) return f.rc;
     return launch_wgrad<T>(c, w, dw_out, f.st, f.slab, raw);
 }
-// can the weight gradient of BN layer i (2..5) run on materialised operands?  (16-bit storage, wide prefetching tile)
+
+// One 3x3 stride-2 layer of the backward on the separate kernels: weight and input gradient of BN layer i from (dz_i, y_i).
+// Layers 7..4 are ConvTranspose2d (the gradient is the high-res tensor, the input gradient a down conv), 3..1 Conv2d (low-res, an
+// up conv).  The other tensor is BN layer i-1's; for layer 4 it is decoder_input's output d0, which has no BatchNorm (identity
+// coefficients, no LeakyReLU) and whose gradient dd0 gets the plain epilogue.
 template <typename T>
-static bool raw_wgrad_ok(vae_ctx* c, int i) {
-    return sizeof(T) == 2 && c->use_raw_wgrad && c->use_pipelined && c->wk.wide && c->wk.tile == 1 && !c->wk.force_simple && i >= 2 && i <= 5;
+static int backward_conv_layer(vae_ctx* c, int i, const float* params, float* grads, hipStream_t st) {
+    const bool convt = i >= 4, from_d0 = i == 4;
+    const BnLayer& l = c->lay[i]; const BnLayer& lp = c->lay[i - 1];   // (lp: not for layer 4)
+    const T* dz = reinterpret_cast<const T*>(l.dz); const T* y = reinterpret_cast<const T*>(l.y); const float* gcoef = l.block + LC_P0 * l.C;
+    const T* yprev = reinterpret_cast<const T*>(from_d0 ? c->d0 : lp.y); const float* cprev = from_d0 ? c->ident : lp.block;
+    const float slope_prev = from_d0 ? 1.f : kSlope; const int Cprev = from_d0 ? 256 : lp.C;
+    const int B = c->fwd.B, Hs = convt ? l.H / 2 : l.H, Ws = convt ? l.W / 2 : l.W;   // the low-res side
+    // weight gradient: s is the low-res operand, g the high-res one
+    WgradArgs<T> w; memset(&w, 0, sizeof(w));
+    if (convt) {
+        w.s0 = yprev; w.scoef = cprev; w.sslope = slope_prev; w.s_two = 0; w.CA = Cprev;
+        w.g0 = dz; w.g1 = y; w.gcoef = gcoef; w.gslope = 1.f; w.g_two = 1; w.CB = l.C;
+    } else {
+        w.s0 = dz; w.s1 = y; w.scoef = gcoef; w.sslope = 1.f; w.s_two = 1; w.CA = l.C;
+        w.g0 = yprev; w.gcoef = cprev; w.gslope = slope_prev; w.g_two = 0; w.CB = Cprev;
+    }
+    w.B = B; w.Hs = Hs; w.Ws = Ws;
+    // input gradient
+    ConvArgs<T> a; memset(&a, 0, sizeof(a));
+    a.src0 = dz; a.src1 = y; a.coef = gcoef; a.slope = 1.f; a.two_src = 1;
+    a.wp = reinterpret_cast<const T*>(c->wp_dg[i]);
+    a.B = B; a.Hs = Hs; a.Ws = Ws; a.Cin = l.C; a.Cout = Cprev;
+    if (from_d0) { a.out = reinterpret_cast<T*>(c->dd0); a.epi = EPI_PLAIN; }
+    else { a.out = reinterpret_cast<T*>(lp.dz); a.yout = yprev; a.ocoef = cprev; a.oslope = kSlope; a.stat = lp.stat_b; a.epi = EPI_BWD; }
+    const auto dgrad = [&] { return convt ? launch_down<T>(c, a, st) : launch_up<T>(c, a, st); };
+    // BatchNorm backward of this layer: folded into both consumers (the input-gradient kernel records it)
+    BnFuse fb;
+    if (bn_bwd_for(c, i, will_pipe(c, a), params, grads, &fb, st)) return -1;
+    w.fuse = fb; a.fuse = fb;
+    const bool skip_wgrad = (c->knob_skip_wgrad >> i) & 1;   // (knob: timing diagnostics)
+    // deep layers: the input-gradient kernel materialises g = BN-backward(dz, y) while staging it; the weight gradient then
+    // reads g and the forward's materialised activation as plain copies (it must follow the input-gradient launch)
+    const bool raw = raw_wgrad_ok<T>(c, i) && l.dy && will_pipe(c, a) && (from_d0 || lp.act_ok);
+    if (raw) {
+        a.stage_out = reinterpret_cast<T*>(l.dy);
+        if (dgrad()) return -1;
+        (convt ? w.g0 : w.s0) = reinterpret_cast<const T*>(l.dy); (convt ? w.s0 : w.g0) = reinterpret_cast<const T*>(from_d0 ? c->d0 : lp.act);
+        w.s1 = w.g1 = nullptr; w.s_two = w.g_two = 0; w.sslope = w.gslope = 1.f; w.fuse.mode = BNF_NONE;
+        return skip_wgrad ? 0 : wgrad_on_side<T>(c, w, grads + c->poff[l.p_convw], st, true);
+    }
+    if (!skip_wgrad && wgrad_on_side<T>(c, w, grads + c->poff[l.p_convw], st)) return -1;
+    return dgrad();
 }
 
 static int bwd_clear_stats(vae_ctx* c, hipStream_t st) {
@@ -775,9 +775,8 @@ static int backward_first(vae_ctx* c, const float* x, const float* params, float
     if (g_xhat || !add_kl) {
         // explicit upstream gradient on xhat (plus, when add_kl, the fused standard-ELBO term)
         const long n = (long)B * H * H;
-        hipLaunchKernelGGL(dlogit_combine_kernel, dim3((unsigned)std::min<long>((n + 255) / 256, 4096)), dim3(256), 0, st,
-                           g_xhat, c->fwd.xhat, add_kl ? c->dlogit : nullptr, gscale, c->dlogit2, n);
-        LAUNCH_CHECK("dlogit_combine_kernel");
+        if (launch("dlogit_combine_kernel", dlogit_combine_kernel, dim3((unsigned)std::min<long>((n + 255) / 256, 4096)), dim3(256), 0, st,
+                   g_xhat, c->fwd.xhat, add_kl ? c->dlogit : nullptr, gscale, c->dlogit2, n)) return -1;
         dl_src = c->dlogit2; dl_scale = nullptr;
     }
     // output conv backward + final_layer BN/LeakyReLU prologue
@@ -794,57 +793,33 @@ static int backward_first(vae_ctx* c, const float* x, const float* params, float
         const bool will_recomp = sizeof(T) == 2 && c->use_mfma_convout && c->use_recomp_dz && convt_fused_ok<T>(c, 7);
         ProfScope ps(c, step7 ? "convout_step(fwd+bce+dgrad+wgrad)" : will_recomp ? "convout_bwd(statistics+wgrad, dz not stored)" : "convout_bwd(dgrad+wgrad+bn prologue)",
                      ((double)sizeof(T) * (will_recomp ? 32 : 64) + (step7 ? 8.0 : 4.0)) * P, (step7 ? 4.0 : 3.0) * 2 * 9 * 32 * P, st);
-        bool launched = false;
+        int rc = 1;   // 1: not launched yet
         if constexpr (sizeof(T) == 2) {
             if (step7 && c->use_convout_stream && H == cos::RW) {
-                // row-streaming form: units = (image, band of RB rows); bands only where whole images would leave CUs idle or the
-                // last round mostly empty (a band costs RB/2 + 3 ticks and restages 4 rows)
+                // row-streaming form: units = (image, band of RB rows); a band costs RB/2 + 3 ticks and restages 4 rows
                 ConvOutStreamArgs<T> m; m.fuse = c->fwd.pending_f7;
                 m.yf = reinterpret_cast<const T*>(c->lay[7].y); m.wt = c->wout_t; m.bias = params + c->poff[39]; m.target = c->fwd.x;
                 m.xhat = c->fwd.xhat; m.accum = c->accum; m.dz = reinterpret_cast<T*>(c->lay[7].dz); m.slab = a.slab; m.stat = a.stat;
                 m.B = B; m.H = H; m.inv_n = (float)(1.0 / ((double)B * H * H)); m.slope = kSlope; m.gmul = c->fwd.gmul;
                 m.dbg = (c->dbg_buf && !strcmp(c->dbg_tag, "final_layer.3")) ? c->dbg_buf : nullptr;
-                const int ncu = 256;
-                long best = -1; int nb = 1;
-                for (int cand = 1; cand <= 16 && H / cand >= 8; cand *= 2) {
-                    const long rounds = ((long)B * cand + ncu - 1) / ncu, cost = rounds * (H / cand / 2 + 3);
-                    if (best < 0 || cost < best) { best = cost; nb = cand; }
-                }
-                if (c->knob_convout_bands > 0 && H % c->knob_convout_bands == 0 && (H / c->knob_convout_bands) % 2 == 0 && H / c->knob_convout_bands >= 8) nb = c->knob_convout_bands;
-                m.nb = nb; m.RB = H / nb; m.n_units = B * nb;
-                grid = std::min(m.n_units, ncu);
-                const size_t lds = convout_stream_lds();
-                if (c->fwd.recon == VAE_RECON_MSE) {
-                    if (set_lds(convout_stream_kernel<T, VAE_RECON_MSE>, lds)) return -1;
-                    hipLaunchKernelGGL((convout_stream_kernel<T, VAE_RECON_MSE>), dim3(grid), dim3(1024), lds, st, m);
-                } else {
-                    if (set_lds(convout_stream_kernel<T, VAE_RECON_BCE>, lds)) return -1;
-                    hipLaunchKernelGGL((convout_stream_kernel<T, VAE_RECON_BCE>), dim3(grid), dim3(1024), lds, st, m);
-                }
-                launched = true;
+                m.nb = stream_bands(B, H, 16, 8, 2, 3);
+                if (c->knob_convout_bands > 0 && H % c->knob_convout_bands == 0 && (H / c->knob_convout_bands) % 2 == 0 && H / c->knob_convout_bands >= 8) m.nb = c->knob_convout_bands;
+                m.RB = H / m.nb; m.n_units = B * m.nb;
+                grid = std::min(m.n_units, 256);
+                rc = pick_recon(c, [&](auto R) { return launch("convout_bwd_kernel", convout_stream_kernel<T, decltype(R)::value>, dim3(grid), dim3(1024), convout_stream_lds(), st, m); });
                 c->fwd.convout_pending = 0;
             }
-            if (step7 && !launched) {
+            else if (step7) {
                 ConvOutStepArgs<T> m; m.fuse = c->fwd.pending_f7; m.rev = (c->knob_rev >> 1) & 1;
                 m.yf = reinterpret_cast<const T*>(c->lay[7].y); m.wt = c->wout_t; m.bias = params + c->poff[39]; m.target = c->fwd.x;
                 m.xhat = c->fwd.xhat; m.accum = c->accum; m.dz = reinterpret_cast<T*>(c->lay[7].dz); m.slab = a.slab; m.stat = a.stat;
                 m.B = B; m.H = H; m.W = H; m.n_tiles = B * (H / 8) * (H / 32);
                 m.inv_n = (float)(1.0 / ((double)B * H * H)); m.slope = kSlope; m.gmul = c->fwd.gmul; m.ablate = c->knob_ablate_f;
                 grid = std::min(m.n_tiles, c->knob_convout_step_grid);   // 512 resident (2 per CU by LDS): two full rounds
-                const size_t lds = convout_step_lds();
-                if (c->fwd.recon == VAE_RECON_MSE) {
-                    if (set_lds(convout_step_mfma_kernel<T, VAE_RECON_MSE>, lds)) return -1;
-                    hipLaunchKernelGGL((convout_step_mfma_kernel<T, VAE_RECON_MSE>), dim3(grid), dim3(256), lds, st, m);
-                } else {
-                    if (set_lds(convout_step_mfma_kernel<T, VAE_RECON_BCE>, lds)) return -1;
-                    hipLaunchKernelGGL((convout_step_mfma_kernel<T, VAE_RECON_BCE>), dim3(grid), dim3(256), lds, st, m);
-                }
-                launched = true;
+                rc = pick_recon(c, [&](auto R) { return launch("convout_bwd_kernel", convout_step_mfma_kernel<T, decltype(R)::value>, dim3(grid), dim3(256), convout_step_lds(), st, m); });
                 c->fwd.convout_pending = 0;
             }
-        }
-        if constexpr (sizeof(T) == 2) {
-            if (!launched && c->use_mfma_convout) {
+            else if (c->use_mfma_convout) {
                 // final_layer.0's gradient kernel can recompute dz from dlogit: then this pass only produces the statistics and
                 // the output conv's weight gradient, and the full-resolution 32-channel dz never goes to HBM
                 recomp7 = c->use_recomp_dz && convt_fused_ok<T>(c, 7);
@@ -853,20 +828,18 @@ static int backward_first(vae_ctx* c, const float* x, const float* params, float
                 m.dz = reinterpret_cast<T*>(c->lay[7].dz); m.slab = a.slab; m.stat = a.stat; m.dbias = a.dbias;
                 m.B = B; m.H = H; m.W = H; m.n_tiles = B * (H / 8) * (H / 32); m.slope = kSlope;
                 grid = std::min(m.n_tiles, c->knob_convout_bwd_grid);
-                hipLaunchKernelGGL((convout_bwd_mfma_kernel<T>), dim3(grid), dim3(256), 0, st, m);
-                launched = true;
+                rc = launch("convout_bwd_kernel", convout_bwd_mfma_kernel<T>, dim3(grid), dim3(256), 0, st, m);
             }
         }
-        if (!launched) hipLaunchKernelGGL((convout_bwd_kernel<T>), dim3(grid), dim3(256), 0, st, a);
+        if (rc == 1) rc = launch("convout_bwd_kernel", convout_bwd_kernel<T>, dim3(grid), dim3(256), 0, st, a);
+        if (rc) return -1;
         cgrid = grid;
-        LAUNCH_CHECK("convout_bwd_kernel");
     }
     {
         SideFork f = fork_side(c, st, 0);   // the kernel above wrote its partial sums into side stream 0's slab
         if (f.rc) return f.rc;
         if (launch_reduce(f.slab, cgrid, 288, grads + c->poff[38], 1, 32, f.st, c)) return -1;
-        hipLaunchKernelGGL(accum_to_f32_kernel, dim3(1), dim3(64), 0, f.st, c->accum + 2, grads + c->poff[39], c->fwd.ginv);
-        LAUNCH_CHECK("accum_to_f32_kernel");
+        if (launch("accum_to_f32_kernel", accum_to_f32_kernel, dim3(1), dim3(64), 0, f.st, c->accum + 2, grads + c->poff[39], c->fwd.ginv)) return -1;
         if (step7 && c->fwd.loss_out3) {   // the ELBO scalars vae_loss_deferred asked for: the BCE sum exists only now
             if (c->kl_shaped() && join_kl(c, f.st)) return -1;
             if (launch_loss_finalize(c, c->fwd.loss_out3, c->fwd.loss_kw, f.st)) return -1;
@@ -882,40 +855,7 @@ static int backward_first(vae_ctx* c, const float* x, const float* params, float
             if (rc < 0) return -1;
             if (rc == 0) continue;
         }
-        const BnLayer& l = c->lay[i];
-        const int Cin = i == 4 ? 256 : c->lay[i - 1].C;
-        WgradArgs<T> w; memset(&w, 0, sizeof(w));
-        if (i == 4) { w.s0 = reinterpret_cast<const T*>(c->d0); w.scoef = c->ident; w.sslope = 1.f; }
-        else { w.s0 = reinterpret_cast<const T*>(c->lay[i - 1].y); w.scoef = c->lay[i - 1].block; w.sslope = kSlope; }
-        w.s_two = 0;
-        w.g0 = reinterpret_cast<const T*>(l.dz); w.g1 = reinterpret_cast<const T*>(l.y); w.gcoef = l.block + LC_P0 * l.C; w.gslope = 1.f; w.g_two = 1;
-        w.B = B; w.Hs = l.H / 2; w.Ws = l.W / 2; w.CA = Cin; w.CB = l.C;
-        ConvArgs<T> a; memset(&a, 0, sizeof(a));
-        a.src0 = reinterpret_cast<const T*>(l.dz); a.src1 = reinterpret_cast<const T*>(l.y); a.coef = l.block + LC_P0 * l.C; a.slope = 1.f; a.two_src = 1;
-        a.wp = reinterpret_cast<const T*>(c->wp_dg[i]);
-        a.B = B; a.Hs = l.H / 2; a.Ws = l.W / 2; a.Cin = l.C; a.Cout = Cin;
-        if (i == 4) { a.out = reinterpret_cast<T*>(c->dd0); a.epi = EPI_PLAIN; }
-        else {
-            a.out = reinterpret_cast<T*>(c->lay[i - 1].dz); a.yout = reinterpret_cast<const T*>(c->lay[i - 1].y);
-            a.ocoef = c->lay[i - 1].block; a.oslope = kSlope; a.stat = c->lay[i - 1].stat_b; a.epi = EPI_BWD;
-        }
-        // BatchNorm backward of this layer: folded into both consumers (the input-gradient kernel records it)
-        BnFuse fb = make_fuse_bwd(c, i, params, grads);
-        if (!(c->use_fused_bn && will_pipe(c, a)) || !c->fwd.trained) { if (bn_bwd_standalone(c, fb, st)) return -1; }
-        w.fuse = fb; a.fuse = fb;
-        // deep layers: the input-gradient kernel materialises g = BN-backward(dz, y) while staging it; the weight gradient then
-        // reads g and the forward's materialised activation as plain copies (it must follow the input-gradient launch)
-        const bool raw = raw_wgrad_ok<T>(c, i) && l.dy && will_pipe(c, a) && (i == 4 || c->lay[i - 1].act_ok);
-        if (raw) {
-            a.stage_out = reinterpret_cast<T*>(l.dy);
-            if (launch_down<T>(c, a, st)) return -1;
-            w.s0 = i == 4 ? reinterpret_cast<const T*>(c->d0) : reinterpret_cast<const T*>(c->lay[i - 1].act); w.s1 = nullptr; w.s_two = 0; w.sslope = 1.f;
-            w.g0 = reinterpret_cast<const T*>(l.dy); w.g1 = nullptr; w.g_two = 0; w.gslope = 1.f; w.fuse.mode = BNF_NONE;
-            if (!((c->knob_skip_wgrad >> i) & 1) && wgrad_on_side<T>(c, w, grads + c->poff[l.p_convw], st, true)) return -1;
-            continue;
-        }
-        if (!((c->knob_skip_wgrad >> i) & 1) && wgrad_on_side<T>(c, w, grads + c->poff[l.p_convw], st)) return -1;   // (knob: timing diagnostics)
-        if (launch_down<T>(c, a, st)) return -1;
+        if (backward_conv_layer<T>(c, i, params, grads, st)) return -1;
     }
     return 0;
 }
@@ -929,36 +869,33 @@ static int backward_second(vae_ctx* c, const float* x, const float* params, floa
                            const float* g_mu, const float* g_lv, const float* g_z, const float* g_pre, float kld_weight, int add_kl,
                            hipStream_t st, int mode = 0, float* out = nullptr) {
     const int B = c->fwd.B, H = c->H, L = c->L;
+    // the non-MFMA weight gradients of the latent block: batch split over grid.z (8 slices) -> slabs -> one reduce per tensor
+    const int nz = std::max(1, std::min(8, B / 8)), bsplit = (B + nz - 1) / nz;
     // decoder_input backward, reparameterisation + KL backward
     c->tag = "latent";
     {
         const bool lat_mfma = (c->use_latent_mfma & 4) && 2 * L <= 9 * 32;   // fc weight gradient path (also produces the bias column sums)
-        if (mode == 1) {}
-        else if ((c->use_latent_mfma & 2) && L + 1 <= 9 * 32) {   // weight + bias gradient in one launch, no slabs (latent_mfma.cuh)
-            SideFork f = fork_side(c, st);
-            if (f.rc) return f.rc;
-            BatchGemmArgs g; memset(&g, 0, sizeof(g));
-            g.X = c->dd0; g.coef = nullptr; g.slope = 1.f; g.Y = c->fwd.z; g.ldy = L; g.ncols = L; g.ones_col = 1;
-            g.out0 = grads + c->poff[20]; g.outb = grads + c->poff[21]; g.B = B; g.F = (int)c->F; g.L = L; g.s2 = c->s2; g.scale = c->fwd.ginv;
-            ProfScope ps(c, "decin_wgrad", (double)sizeof(T) * B * (double)c->F + 4.0 * c->F * L, 2.0 * B * c->F * L, f.st);
-            const size_t lds = batch_gemm_lds();
-            if (set_lds(batch_gemm_kernel<T, false>, lds)) return -1;
-            hipLaunchKernelGGL((batch_gemm_kernel<T, false>), dim3((unsigned)(c->F / 64)), dim3(256), lds, f.st, g);
-            LAUNCH_CHECK("batch_gemm_kernel");
-        } else {
-            // batch split over grid.z (8 slices) -> slabs -> one reduce per tensor
-            const int nz = std::max(1, std::min(8, B / 8)), bsplit = (B + nz - 1) / nz;
+        if (mode != 1) {
+            const bool mfma = (c->use_latent_mfma & 2) && L + 1 <= 9 * 32;   // weight + bias gradient in one launch, no slabs (latent_mfma.cuh)
             SideFork f = fork_side(c, st);
             if (f.rc) return f.rc;
             float* sw = f.slab; float* sb = f.slab + (size_t)nz * c->F * L;
-            dim3 grid((unsigned)(c->F / 256), (L + 31) / 32, nz);
             {
                 ProfScope ps(c, "decin_wgrad", (double)sizeof(T) * B * (double)c->F + 4.0 * c->F * L, 2.0 * B * c->F * L, f.st);
-                hipLaunchKernelGGL((decin_wgrad_kernel<T>), grid, dim3(256), 0, f.st, reinterpret_cast<const T*>(c->dd0), c->fwd.z, sw, sb, B, (int)c->F, L, c->s2, bsplit);
-                LAUNCH_CHECK("decin_wgrad_kernel");
+                if (mfma) {
+                    BatchGemmArgs g; memset(&g, 0, sizeof(g));
+                    g.X = c->dd0; g.coef = nullptr; g.slope = 1.f; g.Y = c->fwd.z; g.ldy = L; g.ncols = L; g.ones_col = 1;
+                    g.out0 = grads + c->poff[20]; g.outb = grads + c->poff[21]; g.B = B; g.F = (int)c->F; g.L = L; g.s2 = c->s2; g.scale = c->fwd.ginv;
+                    if (launch("batch_gemm_kernel", batch_gemm_kernel<T, false>, dim3((unsigned)(c->F / 64)), dim3(256), batch_gemm_lds(), f.st, g)) return -1;
+                } else {
+                    dim3 grid((unsigned)(c->F / 256), (L + 31) / 32, nz);
+                    if (launch("decin_wgrad_kernel", decin_wgrad_kernel<T>, grid, dim3(256), 0, f.st, reinterpret_cast<const T*>(c->dd0), c->fwd.z, sw, sb, B, (int)c->F, L, c->s2, bsplit)) return -1;
+                }
             }
-            if (launch_reduce(sw, nz, (size_t)c->F * L, grads + c->poff[20], 0, 0, f.st, c)) return -1;
-            if (launch_reduce(sb, nz, (size_t)c->F, grads + c->poff[21], 0, 0, f.st, c)) return -1;
+            if (!mfma) {
+                if (launch_reduce(sw, nz, (size_t)c->F * L, grads + c->poff[20], 0, 0, f.st, c)) return -1;
+                if (launch_reduce(sb, nz, (size_t)c->F, grads + c->poff[21], 0, 0, f.st, c)) return -1;
+            }
         }
         int nsplit = 0;
         if (mode == 0 || (mode == 2 && out)) {
@@ -970,102 +907,85 @@ static int backward_second(vae_ctx* c, const float* x, const float* params, floa
         if (mode == 2) {
             if (!out) return join_sides(c, st);
             ProfScope ps(c, "latent_dz", 4.0 * nsplit * B * L + 4.0 * B * L, 0, st);
-            hipLaunchKernelGGL(latent_dz_kernel, dim3((B * L + 255) / 256), dim3(256), 0, st, c->slab, nsplit, c->npad_di, B, L, c->fwd.ginv, out);
-            LAUNCH_CHECK("latent_dz_kernel");
+            if (launch("latent_dz_kernel", latent_dz_kernel, dim3((B * L + 255) / 256), dim3(256), 0, st, c->slab, nsplit, c->npad_di, B, L, c->fwd.ginv, out)) return -1;
             return join_sides(c, st);
         }
         LatentBwdArgs lb;
         lb.slab = c->slab; lb.nslab = nsplit; lb.npad = c->npad_di; lb.mu = c->fwd.mu; lb.lv = c->fwd.lv; lb.eps = c->eps; lb.gscale = gscale;
         lb.gmu = g_mu; lb.glv = g_lv; lb.gz = g_z; lb.dlat = c->dlat; lb.B = B; lb.L = L; lb.kld_weight = kld_weight; lb.add_kl = add_kl; lb.gmul = c->fwd.gmul;
         lb.factor = nullptr; lb.tcg = nullptr; lb.tcw = 0.f;
+        const auto latent_bwd = [&](auto kernel) { return launch("latent_bwd_kernel", kernel, dim3((B * L * LAT_LANES + 255) / 256), dim3(256), 0, st, lb); };
         if (add_kl && c->fwd.kl_kind == VAE_KL_TC) {      // the plain KL gradient plus (tc_weight - 1) times the TC gradient of tc_comp_kernel
             if (join_kl(c, st)) return -1;
             lb.tcg = c->tc_grad(); lb.tcw = (float)(c->fwd.kl_param - 1.0);
-            hipLaunchKernelGGL((latent_bwd_kernel<false, true>), dim3((B * L * LAT_LANES + 255) / 256), dim3(256), 0, st, lb);
+            if (latent_bwd(latent_bwd_kernel<false, true>)) return -1;
         } else if (add_kl && c->fwd.kl_kind != VAE_KL_PLAIN) {   // the objective the forward recorded: its per-dimension factors
             if (join_kl(c, st)) return -1;
             lb.factor = c->kl_factor();
-            hipLaunchKernelGGL(latent_bwd_kernel<true>, dim3((B * L * LAT_LANES + 255) / 256), dim3(256), 0, st, lb);
-        } else hipLaunchKernelGGL(latent_bwd_kernel<false>, dim3((B * L * LAT_LANES + 255) / 256), dim3(256), 0, st, lb);
-        LAUNCH_CHECK("latent_bwd_kernel");
+            if (latent_bwd(latent_bwd_kernel<true>)) return -1;
+        } else if (latent_bwd(latent_bwd_kernel<false>)) return -1;
         if (!lat_mfma) {
             SideFork f = fork_side(c, st);
             if (f.rc) return f.rc;
-            hipLaunchKernelGGL(colsum_kernel, dim3(2 * L), dim3(64), 0, f.st, c->dlat, B, 2 * L, grads + c->poff[17], grads + c->poff[19], L, c->fwd.ginv);
-            LAUNCH_CHECK("colsum_kernel");
+            if (launch("colsum_kernel", colsum_kernel, dim3(2 * L), dim3(64), 0, f.st, c->dlat, B, 2 * L, grads + c->poff[17], grads + c->poff[19], L, c->fwd.ginv)) return -1;
         }
     }
     // fc_mu / fc_var backward: weight gradients (side stream), then the input gradient with encoder.3's LeakyReLU / BatchNorm prologue
-    if ((c->use_latent_mfma & 4) && 2 * L <= 9 * 32) {
-        // both heads' weight gradients + their bias gradients (column sums of dlat) in one launch, no slabs (latent_mfma.cuh)
-        SideFork f = fork_side(c, st);
-        if (f.rc) return f.rc;
-        BatchGemmArgs g; memset(&g, 0, sizeof(g));
-        g.X = c->lay[3].y; g.coef = c->lay[3].block; g.slope = kSlope; g.Y = c->dlat; g.ldy = 2 * L; g.ncols = 2 * L; g.ones_col = 0;
-        g.out0 = grads + c->poff[16]; g.out1 = grads + c->poff[18]; g.colsum0 = grads + c->poff[17]; g.colsum1 = grads + c->poff[19];
-        g.B = B; g.F = (int)c->F; g.L = L; g.s2 = c->s2; g.scale = c->fwd.ginv;
-        ProfScope ps(c, "fc_wgrad", (double)sizeof(T) * B * (double)c->F + 8.0 * c->F * L, 4.0 * B * c->F * L, f.st);
-        const size_t lds = batch_gemm_lds();
-        if (set_lds(batch_gemm_kernel<T, true>, lds)) return -1;
-        hipLaunchKernelGGL((batch_gemm_kernel<T, true>), dim3((unsigned)(c->F / 64)), dim3(256), lds, f.st, g);
-        LAUNCH_CHECK("batch_gemm_kernel");
-    } else {
-        FcWgradArgs<T> w;
-        w.dlat = c->dlat; w.y = reinterpret_cast<const T*>(c->lay[3].y); w.coef = c->lay[3].block; w.slope = kSlope;
-        w.B = B; w.F = (int)c->F; w.L = L; w.s2 = c->s2;
-        const int nz = std::max(1, std::min(8, B / 8));
-        w.bsplit = (B + nz - 1) / nz;
+    {
+        // MFMA form: both heads' weight gradients + their bias gradients (column sums of dlat) in one launch, no slabs (latent_mfma.cuh)
+        const bool mfma = (c->use_latent_mfma & 4) && 2 * L <= 9 * 32;
         SideFork f = fork_side(c, st);   // (no new dependency: the side stream is already past latent_bwd)
         if (f.rc) return f.rc;
         float* smu = f.slab; float* svar = f.slab + (size_t)nz * L * c->F;
-        w.dwmu = smu; w.dwvar = svar;
         {
             ProfScope ps(c, "fc_wgrad", (double)sizeof(T) * B * (double)c->F + 8.0 * c->F * L, 4.0 * B * c->F * L, f.st);
-            hipLaunchKernelGGL((fc_wgrad_kernel<T>), dim3((unsigned)(c->F / 256), (2 * L + 31) / 32, nz), dim3(256), 0, f.st, w);
-            LAUNCH_CHECK("fc_wgrad_kernel");
-        }
-        if (launch_reduce(smu, nz, (size_t)L * c->F, grads + c->poff[16], 0, 0, f.st, c)) return -1;
-        if (launch_reduce(svar, nz, (size_t)L * c->F, grads + c->poff[18], 0, 0, f.st, c)) return -1;
-    }
-    if ((c->use_latent_mfma & 8) && 2 * L <= 256) {
-        RowGemmArgs g; memset(&g, 0, sizeof(g));
-        g.Y = c->dlat; g.ldy = 2 * L; g.K = 2 * L; g.Wp = c->fcpack; g.npad = c->npad_fc; g.out = c->lay[3].dz;
-        g.y = c->lay[3].y; g.ocoef = c->lay[3].block; g.slope = kSlope; g.gpre = g_pre; g.gmul = c->fwd.gmul; g.stat = c->lay[3].stat_b;
-        g.B = B; g.F = (int)c->F; g.s2 = c->s2;
-        ProfScope ps2(c, "fc_dgrad", (double)sizeof(T) * (2.0 * B * c->F + 2.0 * c->F * L), 4.0 * B * c->F * L, st);
-        const size_t lds = row_gemm_lds<T>();
-        if (set_lds(row_gemm_kernel<T, 1>, lds)) return -1;
-        hipLaunchKernelGGL((row_gemm_kernel<T, 1>), dim3((unsigned)(c->F / 64)), dim3(256), lds, st, g);
-        LAUNCH_CHECK("row_gemm_kernel");
-    } else {
-        FcDgradArgs<T> d;
-        d.dlat = c->dlat; d.wp = reinterpret_cast<const T*>(c->fcpack); d.npad = c->npad_fc; d.y = reinterpret_cast<const T*>(c->lay[3].y);
-        d.ocoef = c->lay[3].block; d.slope = kSlope; d.gpre = g_pre; d.dz = reinterpret_cast<T*>(c->lay[3].dz); d.stat = c->lay[3].stat_b;
-        d.B = B; d.F = (int)c->F; d.L2 = 2 * L; d.s2 = c->s2; d.gmul = c->fwd.gmul;
-        ProfScope ps2(c, "fc_dgrad", (double)sizeof(T) * (2.0 * B * c->F + 2.0 * c->F * L), 4.0 * B * c->F * L, st);
-        d.bt_per_wg = std::max(16, ((B + 7) / 8 + 15) / 16 * 16);   // <= 8 workgroups per channel: fewer same-address atomics
-        bool wide = false;
-        if constexpr (sizeof(T) == 2) wide = c->use_fc_dgrad8 && fc_dgrad8_lds(2 * L, 4, 16) <= 64 * 1024;
-        if constexpr (sizeof(T) == 2) {
-            if (wide) {
-                // bit 1: 512-thread workgroups over 64 rows (half the workgroups, half the f64 atomics of the statistics)
-                const bool big = (c->use_fc_dgrad8 & 2) && B > 32;
-                d.bt_per_wg = big ? std::max(64, ((B + 3) / 4 + 63) / 64 * 64) : (d.bt_per_wg + 31) / 32 * 32;
-                const dim3 grid((unsigned)(c->F / 256), (B + d.bt_per_wg - 1) / d.bt_per_wg);
-                if (big) {
-                    if (set_lds(fc_dgrad8_kernel<T, 4, 16>, fc_dgrad8_lds(2 * L, 4, 16))) return -1;
-                    hipLaunchKernelGGL((fc_dgrad8_kernel<T, 4, 16>), grid, dim3(512), fc_dgrad8_lds(2 * L, 4, 16), st, d);
-                } else {
-                    if (set_lds(fc_dgrad8_kernel<T, 4, 8>, fc_dgrad8_lds(2 * L, 4, 8))) return -1;
-                    hipLaunchKernelGGL((fc_dgrad8_kernel<T, 4, 8>), grid, dim3(256), fc_dgrad8_lds(2 * L, 4, 8), st, d);
-                }
-                LAUNCH_CHECK("fc_dgrad8_kernel");
+            if (mfma) {
+                BatchGemmArgs g; memset(&g, 0, sizeof(g));
+                g.X = c->lay[3].y; g.coef = c->lay[3].block; g.slope = kSlope; g.Y = c->dlat; g.ldy = 2 * L; g.ncols = 2 * L; g.ones_col = 0;
+                g.out0 = grads + c->poff[16]; g.out1 = grads + c->poff[18]; g.colsum0 = grads + c->poff[17]; g.colsum1 = grads + c->poff[19];
+                g.B = B; g.F = (int)c->F; g.L = L; g.s2 = c->s2; g.scale = c->fwd.ginv;
+                if (launch("batch_gemm_kernel", batch_gemm_kernel<T, true>, dim3((unsigned)(c->F / 64)), dim3(256), batch_gemm_lds(), f.st, g)) return -1;
+            } else {
+                FcWgradArgs<T> w;
+                w.dlat = c->dlat; w.y = reinterpret_cast<const T*>(c->lay[3].y); w.coef = c->lay[3].block; w.slope = kSlope;
+                w.B = B; w.F = (int)c->F; w.L = L; w.s2 = c->s2; w.bsplit = bsplit; w.dwmu = smu; w.dwvar = svar;
+                if (launch("fc_wgrad_kernel", fc_wgrad_kernel<T>, dim3((unsigned)(c->F / 256), (2 * L + 31) / 32, nz), dim3(256), 0, f.st, w)) return -1;
             }
         }
-        if (!wide) {
-            if (set_lds(fc_dgrad_kernel<T>, fc_dgrad_lds(2 * L))) return -1;
-            hipLaunchKernelGGL((fc_dgrad_kernel<T>), dim3((unsigned)(c->F / 256), (B + d.bt_per_wg - 1) / d.bt_per_wg), dim3(256), fc_dgrad_lds(2 * L), st, d);
-            LAUNCH_CHECK("fc_dgrad_kernel");
+        if (!mfma) {
+            if (launch_reduce(smu, nz, (size_t)L * c->F, grads + c->poff[16], 0, 0, f.st, c)) return -1;
+            if (launch_reduce(svar, nz, (size_t)L * c->F, grads + c->poff[18], 0, 0, f.st, c)) return -1;
+        }
+    }
+    {
+        ProfScope ps(c, "fc_dgrad", (double)sizeof(T) * (2.0 * B * c->F + 2.0 * c->F * L), 4.0 * B * c->F * L, st);
+        if ((c->use_latent_mfma & 8) && 2 * L <= 256) {
+            RowGemmArgs g; memset(&g, 0, sizeof(g));
+            g.Y = c->dlat; g.ldy = 2 * L; g.K = 2 * L; g.Wp = c->fcpack; g.npad = c->npad_fc; g.out = c->lay[3].dz;
+            g.y = c->lay[3].y; g.ocoef = c->lay[3].block; g.slope = kSlope; g.gpre = g_pre; g.gmul = c->fwd.gmul; g.stat = c->lay[3].stat_b;
+            g.B = B; g.F = (int)c->F; g.s2 = c->s2;
+            if (launch("row_gemm_kernel", row_gemm_kernel<T, 1>, dim3((unsigned)(c->F / 64)), dim3(256), row_gemm_lds<T>(), st, g)) return -1;
+        } else {
+            FcDgradArgs<T> d;
+            d.dlat = c->dlat; d.wp = reinterpret_cast<const T*>(c->fcpack); d.npad = c->npad_fc; d.y = reinterpret_cast<const T*>(c->lay[3].y);
+            d.ocoef = c->lay[3].block; d.slope = kSlope; d.gpre = g_pre; d.dz = reinterpret_cast<T*>(c->lay[3].dz); d.stat = c->lay[3].stat_b;
+            d.B = B; d.F = (int)c->F; d.L2 = 2 * L; d.s2 = c->s2; d.gmul = c->fwd.gmul;
+            d.bt_per_wg = std::max(16, ((B + 7) / 8 + 15) / 16 * 16);   // <= 8 workgroups per channel: fewer same-address atomics
+            const auto go = [&](const char* name, auto kernel, int threads, size_t lds) {
+                return launch(name, kernel, dim3((unsigned)(c->F / 256), (B + d.bt_per_wg - 1) / d.bt_per_wg), dim3(threads), lds, st, d);
+            };
+            int rc = 1;   // 1: not launched yet
+            if constexpr (sizeof(T) == 2) {
+                if (c->use_fc_dgrad8 && fc_dgrad8_lds(2 * L, 4, 16) <= 64 * 1024) {
+                    // bit 1: 512-thread workgroups over 64 rows (half the workgroups, half the f64 atomics of the statistics)
+                    const bool big = (c->use_fc_dgrad8 & 2) && B > 32;
+                    d.bt_per_wg = big ? std::max(64, ((B + 3) / 4 + 63) / 64 * 64) : (d.bt_per_wg + 31) / 32 * 32;
+                    rc = big ? go("fc_dgrad8_kernel", fc_dgrad8_kernel<T, 4, 16>, 512, fc_dgrad8_lds(2 * L, 4, 16))
+                             : go("fc_dgrad8_kernel", fc_dgrad8_kernel<T, 4, 8>, 256, fc_dgrad8_lds(2 * L, 4, 8));
+                }
+            }
+            if (rc == 1) rc = go("fc_dgrad_kernel", fc_dgrad_kernel<T>, 256, fc_dgrad_lds(2 * L));
+            if (rc) return -1;
         }
     }
     // encoder stack: Conv2d layers 3, 2, 1 on MFMA, then block 0
@@ -1076,53 +996,28 @@ static int backward_second(vae_ctx* c, const float* x, const float* params, floa
             if (rc < 0) return -1;
             if (rc == 0) continue;
         }
-        const BnLayer& l = c->lay[i]; const BnLayer& lp = c->lay[i - 1];
-        WgradArgs<T> w; memset(&w, 0, sizeof(w));
-        w.s0 = reinterpret_cast<const T*>(l.dz); w.s1 = reinterpret_cast<const T*>(l.y); w.scoef = l.block + LC_P0 * l.C; w.sslope = 1.f; w.s_two = 1;
-        w.g0 = reinterpret_cast<const T*>(lp.y); w.gcoef = lp.block; w.gslope = kSlope; w.g_two = 0;
-        w.B = B; w.Hs = l.H; w.Ws = l.W; w.CA = l.C; w.CB = lp.C;
-        ConvArgs<T> a; memset(&a, 0, sizeof(a));
-        a.src0 = reinterpret_cast<const T*>(l.dz); a.src1 = reinterpret_cast<const T*>(l.y); a.coef = l.block + LC_P0 * l.C; a.slope = 1.f; a.two_src = 1;
-        a.wp = reinterpret_cast<const T*>(c->wp_dg[i]);
-        a.out = reinterpret_cast<T*>(lp.dz); a.yout = reinterpret_cast<const T*>(lp.y); a.ocoef = lp.block; a.oslope = kSlope; a.stat = lp.stat_b; a.epi = EPI_BWD;
-        a.B = B; a.Hs = l.H; a.Ws = l.W; a.Cin = l.C; a.Cout = lp.C;
-        BnFuse fb = make_fuse_bwd(c, i, params, grads);
-        if (!(c->use_fused_bn && will_pipe(c, a)) || !c->fwd.trained) { if (bn_bwd_standalone(c, fb, st)) return -1; }
-        w.fuse = fb; a.fuse = fb;
-        const bool raw = raw_wgrad_ok<T>(c, i) && l.dy && will_pipe(c, a) && lp.act_ok;
-        if (raw) {   // (as in the decoder loop)
-            a.stage_out = reinterpret_cast<T*>(l.dy);
-            if (launch_up<T>(c, a, st)) return -1;
-            w.s0 = reinterpret_cast<const T*>(l.dy); w.s1 = nullptr; w.s_two = 0; w.sslope = 1.f;
-            w.g0 = reinterpret_cast<const T*>(lp.act); w.g1 = nullptr; w.g_two = 0; w.gslope = 1.f; w.fuse.mode = BNF_NONE;
-            if (!((c->knob_skip_wgrad >> i) & 1) && wgrad_on_side<T>(c, w, grads + c->poff[l.p_convw], st, true)) return -1;
-            continue;
-        }
-        if (!((c->knob_skip_wgrad >> i) & 1) && wgrad_on_side<T>(c, w, grads + c->poff[l.p_convw], st)) return -1;   // (knob: timing diagnostics)
-        if (launch_up<T>(c, a, st)) return -1;
+        if (backward_conv_layer<T>(c, i, params, grads, st)) return -1;
     }
     {
         c->tag = kLayerTag[0];
-        BnFuse fb0 = make_fuse_bwd(c, 0, params, grads);
-        if (!c->use_fused_bn || !(c->knob_lean & 2) || !c->fwd.trained) { if (bn_bwd_standalone(c, fb0, st)) return -1; }
+        BnFuse fb0;
+        if (bn_bwd_for(c, 0, (c->knob_lean & 2) != 0, params, grads, &fb0, st)) return -1;
         const long P = (long)B * (H / 2) * (H / 2);
         const int grid = (int)std::min<long>((P / 4 + 63) / 64, 512);   // (a thread takes quads of 4 output pixels)
         // last link of the chain: stays on the caller's stream (a side stream would only add an event round trip)
         SideFork f{st, c->slab, 0};
         {
             ProfScope ps(c, "conv1_wgrad", 4.0 * B * H * H + (double)sizeof(T) * 64.0 * P, 2.0 * 9 * 32 * P, f.st);
-            hipLaunchKernelGGL((conv1_wgrad_kernel<T>), dim3(grid), dim3(256), 0, f.st, x, reinterpret_cast<const T*>(c->lay[0].dz),
-                               reinterpret_cast<const T*>(c->lay[0].y), c->lay[0].block + LC_P0 * 32, f.slab, B, H, H, fb0);
-            LAUNCH_CHECK("conv1_wgrad_kernel");
+            if (launch("conv1_wgrad_kernel", conv1_wgrad_kernel<T>, dim3(grid), dim3(256), 0, f.st, x, reinterpret_cast<const T*>(c->lay[0].dz),
+                       reinterpret_cast<const T*>(c->lay[0].y), c->lay[0].block + LC_P0 * 32, f.slab, B, H, H, fb0)) return -1;
         }
         if (launch_reduce(f.slab, grid, 288, grads + c->poff[0], 32, 1, f.st, c)) return -1;
         if (out) {   // input gradient: reads the p0..p2 the weight-gradient launch above finalised into the block
             if (P >= (1L << 31)) return vae_set_error("vae_backward_ex", "input gradient: batch too large for 32-bit pixel indices");
             const long Q = (P + 63) / 64;
             ProfScope ps(c, "conv1_dgrad", (double)sizeof(T) * 64.0 * P + 4.0 * B * H * H, 2.0 * 9 * 32 * P, st);
-            hipLaunchKernelGGL((conv1_dgrad_kernel<T>), dim3((unsigned)std::min<long>(Q, 2048)), dim3(256), 0, st, reinterpret_cast<const T*>(c->lay[0].dz),
-                               reinterpret_cast<const T*>(c->lay[0].y), c->lay[0].block + LC_P0 * 32, params + c->poff[0], out, B, H, H, c->fwd.ginv);
-            LAUNCH_CHECK("conv1_dgrad_kernel");
+            if (launch("conv1_dgrad_kernel", conv1_dgrad_kernel<T>, dim3((unsigned)std::min<long>(Q, 2048)), dim3(256), 0, st, reinterpret_cast<const T*>(c->lay[0].dz),
+                       reinterpret_cast<const T*>(c->lay[0].y), c->lay[0].block + LC_P0 * 32, params + c->poff[0], out, B, H, H, c->fwd.ginv)) return -1;
         }
     }
     return join_sides(c, st);
@@ -1174,14 +1069,10 @@ int backward_ex_impl(vae_ctx* c, const float* x, const float* params, float* gra
 template <typename T>
 int pre_latents_impl(vae_ctx* c, float* out, hipStream_t st) {
     const long n = (long)c->fwd.B * c->F;
-    hipLaunchKernelGGL((pre_latents_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                       reinterpret_cast<const T*>(c->lay[3].y), c->lay[3].block, kSlope, out, c->fwd.B, (int)c->F, c->s2);
-    LAUNCH_CHECK("pre_latents_kernel");
-    return 0;
+    return launch("pre_latents_kernel", pre_latents_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                  reinterpret_cast<const T*>(c->lay[3].y), c->lay[3].block, kSlope, out, c->fwd.B, (int)c->F, c->s2);
 }
 template <typename T>
 int debug_tensor_impl(vae_ctx* c, const void* src, float* out, long n, int C, int HW, hipStream_t st) {
-    hipLaunchKernelGGL((nhwc_to_nchw_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const T*>(src), out, n, C, HW);
-    LAUNCH_CHECK("nhwc_to_nchw_kernel");
-    return 0;
+    return launch("nhwc_to_nchw_kernel", nhwc_to_nchw_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const T*>(src), out, n, C, HW);
 }
