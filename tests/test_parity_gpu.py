@@ -1526,7 +1526,7 @@ def test_streaming_output_conv_matches_tiled_kernel(dtype, B, bands):
     assert max(worst[n] for n in ("final_layer.3.weight", "final_layer.3.bias", "final_layer.1.weight", "final_layer.1.bias")) < 1e-5, worst
 
 
-def _layer_local_gaps(dtype, H, L, B, gen, seed=41, opts=None, kld_weight=1.0, exact_convout=False, warm=None, keep=None):
+def _layer_local_gaps(dtype, H, L, B, gen, seed=41, opts=None, kld_weight=1.0, exact_convout=False, warm=None, keep=None, x=None, params=None):
     """Every 16-bit kernel of the step against the storage-emulating oracle ON THE KERNEL'S OWN INPUTS: each stored tensor (y_l, dz_l,
     decoder_input's output and gradient) and each parameter gradient is recomputed on the CPU from the tensors the GPU actually
     stored one layer earlier, so a gap is that one kernel's, not the chain's.  (The end-to-end emulation of
@@ -1534,10 +1534,11 @@ def _layer_local_gaps(dtype, H, L, B, gen, seed=41, opts=None, kld_weight=1.0, e
     LeakyReLU slopes a few layers later - DESIGN.md section 4.)  Returns {tensor name: relative L2 gap}.
     warm: batch size of a step run first on the same model, so that the checked step runs in a context sized for that larger batch
     (a model keeps one context for the largest batch it has seen: train_one_epoch's ragged last batch).  keep: a dict that receives
-    the checked step's ELBO scalars and flat gradient."""
+    the checked step's ELBO scalars and flat gradient, its x_hat / mu / log_var / z ("last") and the model.  x, params: the batch
+    (float64 [B, 1, H, H]) and the parameters instead of the default binary pianoroll and perturbed_params (tests/regimes.py)."""
     from torch_vae_amd import _lib
-    p = perturbed_params(L, H, seed, gen)
-    x = vo.synth_pianoroll(B, H, 21).astype(np.float64)
+    p = perturbed_params(L, H, seed, gen) if params is None else params
+    x = vo.synth_pianoroll(B, H, 21).astype(np.float64) if x is None else x
     eps = vo.counter_normal(B * L, 21, 5).reshape(B, L).astype(np.float64)
     m = make_model(H, L, gen, dtype, p, kld_weight=kld_weight)
     for k, v in (opts or {}).items():
@@ -1554,6 +1555,8 @@ def _layer_local_gaps(dtype, H, L, B, gen, seed=41, opts=None, kld_weight=1.0, e
         keep["out3"], keep["grads"] = out3.clone(), m.flat_grads().clone()
     grads = flat_grad_dict(m)
     last = {k: m._last[k].double().cpu().numpy() for k in ("xhat", "mu", "lv", "z")}
+    if keep is not None:
+        keep["last"], keep["model"] = last, m
     C = [32, 64, 128, 256, 128, 64, 32, 32]
     s = H // 16 if gen else 2
     HW = [H // 2, H // 4, H // 8, s, 2 * s, 4 * s, 8 * s, 16 * s]
@@ -1575,6 +1578,8 @@ def _layer_local_gaps(dtype, H, L, B, gen, seed=41, opts=None, kld_weight=1.0, e
         z, cache = vo.bn_train_fwd_stored(Y[i], P(names[i] + ".1.weight"), P(names[i] + ".1.bias"), dtype)
         Z.append(z); CA.append(cache)
     A = [rs(vo.lrelu(z)) for z in Z]                      # staged operands LeakyReLU(BN(y_l)) as the next kernel rounds them
+    if keep is not None:
+        keep["stored"] = {"Y": Y, "DZ": DZ, "Z": Z, "CA": CA}
     gaps = {}
     G = lambda k: grads[k].reshape(p[k].shape).astype(np.float64)   # noqa: E731
     # ---- forward, layer by layer on the GPU's own inputs
