@@ -211,6 +211,30 @@ int vae_log_likelihood(vae_ctx* ctx, const float* x, int batch, const float* par
 int vae_latent_stats(const float* mu, const float* log_var, int64_t n, int latent_dim, int draws, const float* eps, uint64_t seed,
                      double* log_qz, double* log_qz_dims, double* per_dim, double* scalars, vae_stream_t stream);
 
+/* Note-level reconstruction metrics of `rolls` rolls of `roll_len` cells each (xhat, target: [rolls, roll_len] f32, contiguous, any
+ * 4-byte-aligned base - a sliced view is fine), in one pass over both tensors.  Per cell, with xh / tg the f32 values as stored:
+ *   se  = ((double)(xh - tg))^2          ae = |(double)(xh - tg)|          (the f32 difference, widened)
+ *   bce = -(tg max(log xh, -100) + (1 - tg) max(log(1 - xh), -100)) in f32, widened: the ELBO's own BCE term (VAE_RECON_BCE)
+ *   true note:  tg >= target_threshold          predicted note at threshold t:  xh >= thresholds[t]   (f32 against f32)
+ * thresholds: n_thresholds (1..8) finite floats in HOST memory, read before the call returns; unsorted and repeated values are fine.
+ * Device outputs, written in stream order with no host synchronisation:
+ *   roll_sums   [rolls][3] f64            se, ae, bce of each roll
+ *   roll_counts [rolls][1 + 2 n_thresholds] positives (true notes), then tp, fp per threshold (fn = positives - tp,
+ *                                         tn = roll_len - positives - fp)
+ *   totals      [8] f64                   se, ae, bce, n_cells, min xhat, max xhat, min target, max target
+ *   total_counts[1 + 2 n_thresholds]      as roll_counts, over all rolls
+ * accumulate = 1 adds this call to what totals / total_counts hold (sums and counts add, ranges combine; totals whose n_cells is 0 -
+ * all zeros - are the empty state), so an evaluation pass keeps its state on the device; 0 overwrites.  rolls = 0 launches nothing and
+ * with accumulate = 0 zeroes the totals (the roll pointers and xhat / target may then be NULL).  A roll is cut into chunks of 4096
+ * cells, one workgroup each; chunks, rolls and totals are folded in index order without atomics, so the counts are exact and the same
+ * call on the same data gives the same bits.  A NaN xhat is never a predicted note and makes the sums NaN; the ranges skip NaNs.
+ * Returns -1 before anything is enqueued for a null pointer, n_thresholds outside 1..8, a non-finite threshold, rolls < 0,
+ * roll_len < 1 or rolls * ceil(roll_len / 4096) >= 2^31.  Work space (16 bytes per chunk, plus 24 + 8 (1 + 2 n_thresholds) per
+ * chunk when roll_len > 4096) comes from the stream-ordered allocator. */
+int vae_recon_metrics(const float* xhat, const float* target, int64_t rolls, int64_t roll_len, const float* thresholds,
+                      int n_thresholds, float target_threshold, double* roll_sums, int64_t* roll_counts, double* totals,
+                      int64_t* total_counts, int accumulate, vae_stream_t stream);
+
 /* loss.backward() (train.py:650) for the last train-mode forward.
  *   grads: flat f32 buffer, same layout as params; every tensor is overwritten.
  *   use_std: 1 adds the gradient of the standard ELBO of vae_loss (reconstruction term fused in

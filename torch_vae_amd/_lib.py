@@ -24,6 +24,7 @@ KL_FREE_BITS = 1
 KL_CAPACITY = 2
 KL_TC = 3
 TC_MAX_BATCH = 4096   # include/vae_step.h: VAE_KL_TC, vae_total_correlation
+RECON_METRICS_MAX_THRESHOLDS = 8   # include/vae_step.h: vae_recon_metrics
 COMM_ID_BYTES = 128
 GRAD_CLIP_SCRATCH_BYTES = 8192   # include/vae_step.h: VAE_GRAD_CLIP_SCRATCH_BYTES
 
@@ -84,6 +85,7 @@ def lib():
     _sig(L.vae_last_total_correlation, i32, [p, p, p])
     _sig(L.vae_log_likelihood, i32, [p, p, i32, p, p, i32, i32, p, u64, p, p, p, p])
     _sig(L.vae_latent_stats, i32, [p, p, i64, i32, i32, p, u64, p, p, p, p, p])
+    _sig(L.vae_recon_metrics, i32, [p, p, i64, i64, f32p, i32, f32, p, p, p, p, i32, p])
     _sig(L.vae_backward, i32, [p, p, p, p, p, p, p, p, p, p, f32, i32, p])
     _sig(L.vae_backward_part, i32, [p, p, p, p, p, p, p, p, p, p, f32, i32, i32, p])
     _sig(L.vae_encode, i32, [p, p, i32, p, p, p, p, u64, i32, p, p, p, p])
@@ -123,6 +125,7 @@ EXPORTS = [
     "vae_last_error", "vae_abi_version", "vae_param_layout", "vae_bn_layout", "vae_create", "vae_destroy",
     "vae_workspace_bytes", "vae_forward", "vae_decode", "vae_pre_latents", "vae_last_eps", "vae_loss", "vae_loss_deferred", "vae_elbo_generic",
     "vae_set_recon_loss", "vae_elbo_generic_ex", "vae_set_kl_objective", "vae_elbo_generic_kl", "vae_kl_per_dim", "vae_total_correlation", "vae_last_total_correlation", "vae_log_likelihood", "vae_latent_stats",
+    "vae_recon_metrics",
     "vae_backward", "vae_backward_part", "vae_encode", "vae_backward_ex", "vae_comm_stream", "vae_comm_unique_id", "vae_comm_init", "vae_comm_world",
     "vae_comm_destroy", "vae_allreduce_grads", "vae_broadcast_state", "vae_adamw_step", "vae_train_step", "vae_train_step_fused",
     "vae_grad_norm", "vae_adamw_step_clipped", "vae_train_step_fused_clipped", "vae_synth_pianoroll", "vae_expand_stimuli", "vae_profile",

@@ -6,6 +6,7 @@
 #include "edge_kernels.cuh"
 #include "loglik.cuh"
 #include "latent_stats.cuh"
+#include "recon_metrics.cuh"
 #include "grad_clip.cuh"
 #include "total_corr.cuh"
 
@@ -788,6 +789,78 @@ extern "C" int vae_latent_stats(const float* mu, const float* lv, int64_t n, int
         LAUNCH_CHECK("lstat_moments_kernel");
         hipLaunchKernelGGL(lstat_final_kernel, dim3(1), dim3(256), 0, st, log_qz, SN, dstat, L, scalars);
         LAUNCH_CHECK("lstat_final_kernel");
+        return 0;
+    };
+    const int rc = run();
+    const hipError_t fe = hipFreeAsync(ws, st);
+    if (rc) return rc;
+    if (fe != hipSuccess) return vae_set_error("hipFreeAsync", hipGetErrorString(fe));
+    return 0;
+}
+
+// Note-level reconstruction metrics (recon_metrics.cuh).  Two launches: the pass over the cells, one workgroup per (roll, chunk), and
+// the fold of chunks into rolls and of rolls into the totals, one wave per output field.  The per-chunk ranges (and, for rolls longer than one
+// chunk, the per-chunk sums and counts) go through the stream-ordered allocator; nothing is read back.
+template <int T>
+static int recon_metrics_launch(std::integral_constant<int, T>, unsigned grid, hipStream_t st, const float* xhat, const float* target,
+                                long roll_len, long nchunks, const RmThresholds& th, float tt, double* ps, long long* pc, float* pr) {
+    hipLaunchKernelGGL(recon_metrics_kernel<T>, dim3(grid), dim3(RM_THREADS), 0, st, xhat, target, roll_len, nchunks, th, tt, ps, pc, pr);
+    LAUNCH_CHECK("recon_metrics_kernel");
+    return 0;
+}
+extern "C" int vae_recon_metrics(const float* xhat, const float* target, int64_t rolls, int64_t roll_len, const float* thresholds,
+                                 int n_thresholds, float target_threshold, double* roll_sums, int64_t* roll_counts, double* totals,
+                                 int64_t* total_counts, int accumulate, vae_stream_t stream) {
+    const char* what = "vae_recon_metrics";
+    if (!thresholds || !totals || !total_counts) return vae_set_error(what, "null pointer (thresholds, totals, total_counts)");
+    if (n_thresholds < 1 || n_thresholds > RM_MAX_T) return vae_set_error(what, "n_thresholds must be in 1..8");
+    RmThresholds th{};
+    for (int k = 0; k < n_thresholds; ++k) {
+        if (!std::isfinite(thresholds[k])) return vae_set_error(what, "thresholds must be finite");
+        th.t[k] = thresholds[k];
+    }
+    if (!std::isfinite(target_threshold)) return vae_set_error(what, "target_threshold must be finite");
+    if (rolls < 0) return vae_set_error(what, "rolls must be >= 0");
+    if (roll_len < 1) return vae_set_error(what, "roll_len must be >= 1");
+    if (accumulate != 0 && accumulate != 1) return vae_set_error(what, "accumulate must be 0 or 1");
+    hipStream_t st = (hipStream_t)stream;
+    const int ncnt = 1 + 2 * n_thresholds;
+    if (rolls == 0) {
+        if (!accumulate) {
+            HIP_CHECK_RET(hipMemsetAsync(totals, 0, 8 * sizeof(double), st));
+            HIP_CHECK_RET(hipMemsetAsync(total_counts, 0, ncnt * sizeof(int64_t), st));
+        }
+        return 0;
+    }
+    if (!xhat || !target || !roll_sums || !roll_counts) return vae_set_error(what, "null pointer (xhat, target, roll_sums, roll_counts)");
+    if ((reinterpret_cast<uintptr_t>(xhat) | reinterpret_cast<uintptr_t>(target)) & 3) return vae_set_error(what, "xhat and target must be 4-byte aligned");
+    const int64_t nchunks = (roll_len - 1) / RM_CHUNK + 1;
+    if (rolls > INT32_MAX / nchunks) return vae_set_error(what, "rolls * ceil(roll_len / 4096) must stay below 2^31");
+    if (roll_len > ((int64_t)1 << 52) / rolls) return vae_set_error(what, "rolls * roll_len must stay below 2^52");
+    const size_t np = (size_t)(rolls * nchunks);
+    const size_t rng_bytes = (np * 4 * sizeof(float) + 255) / 256 * 256, sum_bytes = (np * 3 * sizeof(double) + 255) / 256 * 256;
+    const bool split = nchunks > 1;
+    void* ws = nullptr;
+    HIP_CHECK_RET(hipMallocAsync(&ws, rng_bytes + (split ? sum_bytes + np * ncnt * sizeof(int64_t) : 0), st));
+    char* base = static_cast<char*>(ws);
+    float* pr = reinterpret_cast<float*>(base);
+    double* ps = split ? reinterpret_cast<double*>(base + rng_bytes) : roll_sums;
+    long long* pc = split ? reinterpret_cast<long long*>(base + rng_bytes + sum_bytes) : reinterpret_cast<long long*>(roll_counts);
+    auto run = [&]() -> int {
+        auto go = [&](auto t) {
+            return recon_metrics_launch(t, (unsigned)np, st, xhat, target, (long)roll_len, (long)nchunks, th, target_threshold, ps, pc, pr);
+        };
+        int rc = 0;   // the threshold count is a template argument: the counters stay in registers
+        switch (n_thresholds) {
+#define RM_CASE(T) case T: rc = go(std::integral_constant<int, T>{}); break;
+            RM_CASE(1) RM_CASE(2) RM_CASE(3) RM_CASE(4) RM_CASE(5) RM_CASE(6) RM_CASE(7) RM_CASE(8)
+#undef RM_CASE
+        }
+        if (rc) return rc;
+        hipLaunchKernelGGL(recon_metrics_fold_kernel, dim3(1 + (3 + ncnt + 3) / 4), dim3(RM_THREADS), 0, st, (long)rolls, (long)nchunks, ncnt,
+                           (double)rolls * (double)roll_len, ps, pc, pr, roll_sums, reinterpret_cast<long long*>(roll_counts), totals,
+                           reinterpret_cast<long long*>(total_counts), accumulate);
+        LAUNCH_CHECK("recon_metrics_fold_kernel");
         return 0;
     };
     const int rc = run();

@@ -4,12 +4,16 @@ running statistics) through the HIP kernels; MSE / MAE are reduced on the device
 sklearn on the host (same definitions, converted to percentages as the reference does)."""
 from __future__ import annotations
 
+import ctypes
+import math
+
 import torch
 
 from . import _lib
-from .types_helpers import LatentStatsOutput
+from .types_helpers import LatentStatsOutput, ReconMetricsOutput
 
 MAX_LATENT_DIM = 4096
+MAX_NOTE_THRESHOLDS = _lib.RECON_METRICS_MAX_THRESHOLDS
 
 
 def latent_statistics(mu, log_var, *, draws=1, eps=None, seed=0, active_threshold=0.01) -> LatentStatsOutput:
@@ -68,12 +72,165 @@ def latent_statistics(mu, log_var, *, draws=1, eps=None, seed=0, active_threshol
                              dwkl_per_dim=per_dim[2], log_qz=log_qz, log_qz_dims=log_qz_dims)
 
 
-def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nll_samples=0, latent_rolls=0):
+def _note_thresholds(thresholds, target_threshold):
+    """(thresholds rounded to float32 once, as Python floats; the same for target_threshold).  A float stands for a list of one."""
+    if isinstance(thresholds, (int, float)) and not isinstance(thresholds, bool):
+        thresholds = (thresholds,)
+    try:
+        ts = [float(t) for t in thresholds]
+    except (TypeError, ValueError):
+        raise ValueError(f"thresholds must be a float or a sequence of floats, got {thresholds!r}") from None
+    if not 1 <= len(ts) <= MAX_NOTE_THRESHOLDS:
+        raise ValueError(f"need 1 to {MAX_NOTE_THRESHOLDS} thresholds, got {len(ts)}")
+    tt = float(target_threshold)
+    if not all(math.isfinite(t) for t in ts) or not math.isfinite(tt):
+        raise ValueError(f"thresholds and target_threshold must be finite, got {ts} and {tt}")
+    f32 = lambda v: ctypes.c_float(v).value
+    ts, tt = tuple(f32(t) for t in ts), f32(tt)
+    if not all(math.isfinite(t) for t in ts) or not math.isfinite(tt):
+        raise ValueError("thresholds and target_threshold must be finite in float32")
+    return ts, tt
+
+
+def _checked_rolls(xhat, target):
+    """The two tensors as the kernel reads them ([N, roll_len] float32, contiguous, on one GPU) and (N, roll_len)."""
+    if not isinstance(xhat, torch.Tensor) or not isinstance(target, torch.Tensor):
+        raise TypeError("xhat and target must be tensors")
+    if xhat.dim() < 1 or tuple(xhat.shape) != tuple(target.shape):
+        raise ValueError(f"xhat and target must have the same shape [N, ...], got {tuple(xhat.shape)} and {tuple(target.shape)}")
+    if xhat.dtype != torch.float32 or target.dtype != torch.float32:
+        raise TypeError(f"xhat and target must be float32, got {xhat.dtype} and {target.dtype}")
+    if xhat.device.type != "cuda" or target.device != xhat.device:
+        raise ValueError("xhat and target must be on the same GPU: the metrics run on the HIP kernels only")
+    n = xhat.shape[0]
+    roll_len = 1
+    for s in xhat.shape[1:]:
+        roll_len *= s
+    if roll_len < 1:
+        raise ValueError(f"a roll must have at least one cell, got shape {tuple(xhat.shape)}")
+    return xhat.detach().contiguous(), target.detach().contiguous(), n, roll_len
+
+
+def _recon_metrics_call(xhat, target, n, roll_len, c_thresholds, tt, roll_sums, roll_counts, totals, total_counts, accumulate):
+    dev = xhat.device
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().vae_recon_metrics(
+            xhat.data_ptr(), target.data_ptr(), n, roll_len, c_thresholds, len(c_thresholds), tt, roll_sums.data_ptr(),
+            roll_counts.data_ptr(), totals.data_ptr(), total_counts.data_ptr(), int(accumulate),
+            torch.cuda.current_stream(dev).cuda_stream), "vae_recon_metrics")
+
+
+def ratios_from_counts(n_cells, positives, tp, fp):
+    """Per-threshold note ratios from the counts of vae_recon_metrics (host integers; tp, fp sequences of equal length):
+    precision = tp / (tp + fp), recall = tp / (tp + fn), f1 = 2 tp / (2 tp + fp + fn), accuracy = (tp + tn) / n_cells,
+    pred_density = (tp + fp) / n_cells, with fn = positives - tp and tn = n_cells - positives - fp.  A ratio whose denominator
+    is 0 is 0.0 (scikit-learn's zero_division=0).  Returns a dict of lists."""
+    n_cells, positives = int(n_cells), int(positives)
+    div = lambda a, b: a / b if b else 0.0
+    out = {k: [] for k in ("precision", "recall", "f1", "accuracy", "pred_density")}
+    for t, f in zip(tp, fp):
+        t, f = int(t), int(f)
+        fn = positives - t
+        out["precision"].append(div(t, t + f))
+        out["recall"].append(div(t, t + fn))
+        out["f1"].append(div(2 * t, 2 * t + f + fn))
+        out["accuracy"].append(div(t + (n_cells - positives - f), n_cells))
+        out["pred_density"].append(div(t + f, n_cells))
+    return out
+
+
+def reconstruction_metrics(xhat, target, thresholds=(0.5,), *, target_threshold=0.5) -> ReconMetricsOutput:
+    """Note-level reconstruction metrics of N rolls in one HIP pass (include/vae_step.h: vae_recon_metrics).  xhat, target: float32
+    GPU tensors of equal shape [N, ...], dimension 0 indexing rolls.  A cell is a true note iff target >= target_threshold and a
+    predicted note at threshold t iff xhat >= t (float32 comparisons; up to 8 thresholds, in any order).  Returns device tensors,
+    with no host synchronisation: the sums se, ae, bce (float64; bce is the ELBO's BCE term, nats), n_cells, positives, tp / fp / fn
+    [T] (int64), xhat_range and target_range (min, max), and the per-roll partials they were folded from (roll_se, roll_ae,
+    roll_bce, roll_positives [N], roll_tp, roll_fp [N, T]) - rank rolls by them.  Counts are exact; every sum runs in a fixed order,
+    so repeated calls are bit-identical.  Not differentiable."""
+    ts, tt = _note_thresholds(thresholds, target_threshold)
+    xhat, target, n, roll_len = _checked_rolls(xhat, target)
+    T, dev = len(ts), xhat.device
+    roll_sums = torch.empty(n, 3, device=dev, dtype=torch.float64)
+    roll_counts = torch.empty(n, 1 + 2 * T, device=dev, dtype=torch.int64)
+    totals = torch.empty(8, device=dev, dtype=torch.float64)
+    total_counts = torch.empty(1 + 2 * T, device=dev, dtype=torch.int64)
+    _recon_metrics_call(xhat, target, n, roll_len, (ctypes.c_float * T)(*ts), tt, roll_sums, roll_counts, totals, total_counts, 0)
+    tp = total_counts[1::2]
+    return ReconMetricsOutput(
+        se=totals[0], ae=totals[1], bce=totals[2], n_cells=totals[3].to(torch.int64), positives=total_counts[0], tp=tp,
+        fp=total_counts[2::2], fn=total_counts[0] - tp, xhat_range=totals[4:6], target_range=totals[6:8],
+        roll_se=roll_sums[:, 0], roll_ae=roll_sums[:, 1], roll_bce=roll_sums[:, 2], roll_positives=roll_counts[:, 0],
+        roll_tp=roll_counts[:, 1::2], roll_fp=roll_counts[:, 2::2])
+
+
+class ReconMetricsAccumulator:
+    """reconstruction_metrics over a whole pass: update() adds a batch to totals that stay on the device (one library call, no host
+    synchronisation, no allocation beyond the per-roll work space, which is reused while the batch size stays the same); compute()
+    reads them back once."""
+
+    def __init__(self, thresholds=(0.5,), target_threshold=0.5, device="cuda"):
+        self.thresholds, self.target_threshold = _note_thresholds(thresholds, target_threshold)
+        self.device = torch.device(device)
+        self._c_thresholds = (ctypes.c_float * len(self.thresholds))(*self.thresholds)
+        self._state = None     # 8 float64 totals then 1 + 2T int64 counts, one buffer: one read in compute()
+        self._roll = None      # (n, roll_sums, roll_counts)
+
+    def _views(self):
+        if self._state is None:
+            self._state = torch.zeros(8 + 1 + 2 * len(self.thresholds), device=self.device, dtype=torch.int64)
+        return self._state[:8].view(torch.float64), self._state[8:]
+
+    def reset(self):
+        if self._state is not None:
+            self._state.zero_()     # all zeros is the kernels' empty state (n_cells == 0)
+
+    def update(self, xhat, target):
+        xhat, target, n, roll_len = _checked_rolls(xhat, target)
+        if xhat.device != self._views()[0].device:
+            raise ValueError(f"the accumulator lives on {self._state.device}, the tensors on {xhat.device}")
+        totals, counts = self._views()
+        if self._roll is None or self._roll[0] != n:
+            self._roll = (n, torch.empty(n, 3, device=xhat.device, dtype=torch.float64),
+                          torch.empty(n, counts.numel(), device=xhat.device, dtype=torch.int64))
+        _recon_metrics_call(xhat, target, n, roll_len, self._c_thresholds, self.target_threshold, self._roll[1], self._roll[2],
+                            totals, counts, 1)
+
+    def totals(self) -> dict:
+        """The running totals as device tensors (views of the state, no host synchronisation), under ReconMetricsOutput's keys."""
+        t, c = self._views()
+        tp = c[1::2]
+        return dict(se=t[0], ae=t[1], bce=t[2], n_cells=t[3].to(torch.int64), positives=c[0], tp=tp, fp=c[2::2], fn=c[0] - tp,
+                    xhat_range=t[4:6], target_range=t[6:8])
+
+    def compute(self) -> dict:
+        """Python numbers: count_cells, mse, mae, bce (means per cell; bce in nats), note_density, xhat_range and target_range
+        (min, max), and per threshold the lists precision, recall, f1, accuracy, pred_density (ratios_from_counts)."""
+        T = len(self.thresholds)
+        if self._state is None:
+            tot, cnt = [0.0] * 8, [0] * (1 + 2 * T)
+        else:
+            host = self._state.cpu()
+            tot, cnt = host[:8].view(torch.float64).tolist(), host[8:].tolist()
+        n = int(tot[3])
+        d = max(n, 1)
+        out = {"count_cells": n, "mse": tot[0] / d, "mae": tot[1] / d, "bce": tot[2] / d, "note_density": cnt[0] / d,
+               "xhat_range": (tot[4], tot[5]), "target_range": (tot[6], tot[7])}
+        out.update(ratios_from_counts(n, cnt[0], cnt[1::2], cnt[2::2]))
+        return out
+
+
+def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nll_samples=0, latent_rolls=0, note_thresholds=None):
     """nll_samples = K > 0 adds ``nll`` (mean over the samples of -log p(x), importance-weighted with K draws) and ``elbo``
     (mean per-sample ELBO), both in nats per roll (VanillaVAE.log_likelihood); 0 leaves keys, values and printout as the
     reference has them.  latent_rolls = R > 0 keeps the eval forward's own mu / log_var of the first R rolls (loader order)
     and adds ``kl``, ``mi``, ``tc``, ``dwkl`` (nats) and ``active_units`` from latent_statistics on them (default draws and
-    seed); 0 leaves everything as it is.  Under torch.distributed each rank reports its own shard."""
+    seed); 0 leaves everything as it is.  note_thresholds = a float or up to 8 of them routes every reconstruction reduction of
+    the pass through one ReconMetricsAccumulator (one HIP pass per batch, nothing read back until the end; ``mse``, ``mae`` and the
+    printed ranges come from it) and adds ``bce`` (nats per cell, the ELBO's reconstruction term), ``precision``, ``recall``, ``f1``
+    (percent, a note being a cell >= 0.5 in the stimulus and >= note_thresholds[0] in the output), ``note_density`` (percent) and,
+    with more than one threshold, ``best_f1`` (percent) and the ``best_threshold`` that gives it; None leaves everything as it is.
+    Under torch.distributed each rank reports its own shard."""
+    notes = None if note_thresholds is None else ReconMetricsAccumulator(note_thresholds, device=device)
     if isinstance(latent_rolls, bool) or int(latent_rolls) != latent_rolls or latent_rolls < 0:
         raise ValueError(f"latent_rolls must be an integer >= 0, got {latent_rolls}")
     model.eval()
@@ -104,6 +261,10 @@ def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nl
             nll_sum -= lk["log_likelihood"].sum()
             elbo_sum += lk["elbo"].sum()
         rec = output["output"]
+        if notes is not None:
+            notes.update(rec, stimuli if stimuli.dtype == torch.float32 else stimuli.float())
+            n_seen += stimuli.shape[0]
+            continue
         d = (rec - stimuli).double()
         se += (d * d).sum()
         ae += d.abs().sum()
@@ -111,14 +272,28 @@ def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nl
         n_seen += stimuli.shape[0]
         stim_min, stim_max = min(stim_min, float(stimuli.min())), max(stim_max, float(stimuli.max()))
         rec_min, rec_max = min(rec_min, float(rec.min())), max(rec_max, float(rec.max()))
+    if notes is not None:
+        nm = notes.compute()
+        (stim_min, stim_max), (rec_min, rec_max) = nm["target_range"], nm["xhat_range"]
+        if not nm["count_cells"]:
+            stim_min, stim_max, rec_min, rec_max = float("inf"), float("-inf"), float("inf"), float("-inf")
     if verbosity >= 1:
         print(f"input has range  [{stim_min:.03f}, {stim_max:.03f}]")
         print(f"output has range [{rec_min:.03f}, {rec_max:.03f}]")
     results = {"count": n_seen}
     # F.cross_entropy(reconstruction, stimuli) over the single channel C=1 is identically 0 (evaluation.py:66)
     results["cross-entropy"] = 0.0
-    results["mse"] = 100.0 * float(se) / max(n_elem, 1)
-    results["mae"] = 100.0 * float(ae) / max(n_elem, 1)
+    if notes is None:
+        results["mse"] = 100.0 * float(se) / max(n_elem, 1)
+        results["mae"] = 100.0 * float(ae) / max(n_elem, 1)
+    else:
+        results["mse"], results["mae"], results["bce"] = 100.0 * nm["mse"], 100.0 * nm["mae"], nm["bce"]
+        for k in ("precision", "recall", "f1"):
+            results[k] = 100.0 * nm[k][0]
+        results["note_density"] = 100.0 * nm["note_density"]
+        if len(notes.thresholds) > 1:
+            best = max(range(len(notes.thresholds)), key=lambda i: nm["f1"][i])     # the first of equals
+            results["best_f1"], results["best_threshold"] = 100.0 * nm["f1"][best], notes.thresholds[best]
     if nll_samples:
         results["nll"] = float(nll_sum) / max(n_seen, 1)
         results["elbo"] = float(elbo_sum) / max(n_seen, 1)
@@ -131,8 +306,10 @@ def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nl
         for k, v in results.items():
             if "count" in k or k == "active_units":
                 print(f"  {k + ' ':.<21s}{v:7d}")
-            elif "entropy" in k:
+            elif "entropy" in k or k == "bce":
                 print(f"  {k + ' ':.<24s} {v:9.5f} nat")
+            elif k == "best_threshold":
+                print(f"  {k + ' ':.<24s} {v:9.5f}")
             elif k in ("nll", "elbo", "kl", "mi", "tc", "dwkl"):
                 print(f"  {k + ' ':.<24s} {v:9.3f} nat")
             else:

@@ -40,3 +40,22 @@ class LatentStatsOutput(TypedDict):
     dwkl_per_dim: Tensor      # [L] float64
     log_qz: Tensor            # [S, N] float64: log q(z) at each draw
     log_qz_dims: Tensor       # [S, N, L] float64: log q(z_d) at each draw
+
+
+class ReconMetricsOutput(TypedDict):
+    se: Tensor                # 0-d float64: sum over cells of (xhat - target)^2 (the f32 difference, widened)
+    ae: Tensor                # 0-d float64: sum of |xhat - target|
+    bce: Tensor               # 0-d float64: sum of the ELBO's BCE term (nats)
+    n_cells: Tensor           # 0-d int64
+    positives: Tensor         # 0-d int64: true notes (target >= target_threshold)
+    tp: Tensor                # [T] int64: true and predicted (xhat >= thresholds[t])
+    fp: Tensor                # [T] int64: predicted, not true
+    fn: Tensor                # [T] int64: true, not predicted
+    xhat_range: Tensor        # [2] float64: min, max
+    target_range: Tensor      # [2] float64: min, max
+    roll_se: Tensor           # [N] float64
+    roll_ae: Tensor           # [N] float64
+    roll_bce: Tensor          # [N] float64
+    roll_positives: Tensor    # [N] int64
+    roll_tp: Tensor           # [N, T] int64
+    roll_fp: Tensor           # [N, T] int64
