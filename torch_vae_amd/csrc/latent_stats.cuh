@@ -1,4 +1,4 @@
-// Latent-space diagnostics (vae_latent_stats, vae_api.hip): the aggregate posterior q(z) = 1/N sum_j q(z|x_j) of N encoded rolls,
+// Latent-space diagnostics (vae_latent_stats, vae_util.hip): the aggregate posterior q(z) = 1/N sum_j q(z|x_j) of N encoded rolls,
 // evaluated at S draws z ~ q(z|x_i) per roll, whole (log q(z)) and per dimension (log q(z_d)).  From these and the analytic terms the
 // f64 kernels at the end form KL, MI = I(x;z), TC and dimension-wise KL (beta-TCVAE decomposition, Chen et al. 2018), and the
 // per-dimension moments behind active units (Burda et al. 2016).

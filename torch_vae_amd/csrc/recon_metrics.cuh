@@ -1,4 +1,4 @@
-// Note-level reconstruction metrics (vae_recon_metrics, vae_api.hip): one pass over (xhat, target) gives, per roll and in total, the
+// Note-level reconstruction metrics (vae_recon_metrics, vae_util.hip): one pass over (xhat, target) gives, per roll and in total, the
 // f64 sums of the squared error, the absolute error and the ELBO's own BCE term, the number of true notes, and for up to RM_MAX_T
 // output thresholds the true / false positives; plus the value ranges of both tensors.
 //   recon_metrics_kernel<T>: one workgroup per (roll, chunk of RM_CHUNK cells).  A lane reads 16 bytes of each tensor per step (a

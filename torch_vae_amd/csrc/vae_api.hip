@@ -1,12 +1,11 @@
 // Context and the C ABI (include/vae_step.h) of the VAE step.  The launch sequencing is templated on the storage
-// type and lives in vae_impl.cuh, instantiated by impl_bf16.hip / impl_f16.hip / impl_f32.hip.
+// type and lives in vae_impl.cuh, instantiated by impl_bf16.hip / impl_f16.hip / impl_f32.hip.  The entry points that need neither the
+// context nor a helper of this file are in vae_util.hip.
 #include <map>
 #include <mutex>
 #include "vae_ctx.h"
 #include "edge_kernels.cuh"
 #include "loglik.cuh"
-#include "latent_stats.cuh"
-#include "recon_metrics.cuh"
 #include "grad_clip.cuh"
 #include "total_corr.cuh"
 
@@ -285,85 +284,16 @@ int join_comm(vae_ctx* c, hipStream_t st) {
     c->comm_busy = 0;
     return 0;
 }
-// data_generators.py:45-77 restated with the counter generator (stream 777); one workgroup per image
-__global__ void synth_pianoroll_kernel(float* x, int H, unsigned long long seed, int max_lines) {
-    const int b = blockIdx.x;
-    const int width = 1 + (int)(counter_uniform(0, seed, 777) * 4);
-    const unsigned long long base = 1 + (unsigned long long)b * (1 + 4 * max_lines);
-    const int n_lines = 1 + (int)(counter_uniform(base, seed, 777) * max_lines);
-    for (int p = threadIdx.x; p < H * H; p += blockDim.x) {
-        const int py = p / H, px = p % H;
-        float v = 0.f;
-        for (int li = 0; li < n_lines; ++li) {
-            const unsigned long long k = base + 1 + 4ULL * li;
-            const bool vert = counter_uniform(k, seed, 777) < 0.5;
-            const int pos = (int)(counter_uniform(k + 1, seed, 777) * H);
-            const int start = (int)(counter_uniform(k + 2, seed, 777) * H);
-            const int end = start + (int)(counter_uniform(k + 3, seed, 777) * (H - start));
-            const int lo = max(0, pos - width / 2), hi = min(H, pos + width / 2 + 1);
-            const int along = vert ? py : px, across = vert ? px : py;
-            if (along >= start && along < end && across >= lo && across < hi) v = 1.f;
-        }
-        x[(size_t)b * H * H + p] = v;
-    }
-}
-extern "C" int vae_synth_pianoroll(float* x, int B, int H, uint64_t seed, vae_stream_t stream) {
-    hipLaunchKernelGGL(synth_pianoroll_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, x, H, (unsigned long long)seed, 20);
-    LAUNCH_CHECK("synth_pianoroll_kernel");
-    return 0;
-}
-
-
-// Byte / bit-plane stimuli -> the float32 batch the kernels read (train.py:630 copies float32 stimuli; pianorolls are 0/1 cells).
-// kind 0: one byte per cell (uint8 / bool), value v -> (float)v; kind 1: bit planes, most significant bit first (numpy.packbits
-// order), bit -> 0.f / 1.f.  The source may be device memory or PINNED host memory: the kernel then reads the batch straight over
-// the host link (0.5 MB of bit planes or 4 MB of bytes for 256 images of 128x128), which removes the separate copy and its
-// queue hand-over from the step's dependent chain.
-__global__ void expand_bytes_kernel(const uint32_t* __restrict__ src, float* __restrict__ dst, long n4) {
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-        const uint32_t w = __builtin_nontemporal_load(src + i);
-        *reinterpret_cast<f32x4*>(dst + 4 * i) = f32x4{(float)(w & 255u), (float)((w >> 8) & 255u), (float)((w >> 16) & 255u), (float)(w >> 24)};
-    }
-}
-__global__ void expand_bits_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst, long nbytes) {
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < nbytes; i += (long)gridDim.x * blockDim.x) {
-        const uint32_t w = __builtin_nontemporal_load(src + i);
-        *reinterpret_cast<f32x4*>(dst + 8 * i) = f32x4{(float)((w >> 7) & 1u), (float)((w >> 6) & 1u), (float)((w >> 5) & 1u), (float)((w >> 4) & 1u)};
-        *reinterpret_cast<f32x4*>(dst + 8 * i + 4) = f32x4{(float)((w >> 3) & 1u), (float)((w >> 2) & 1u), (float)((w >> 1) & 1u), (float)(w & 1u)};
-    }
-}
-extern "C" int vae_expand_stimuli(const void* src, int kind, float* dst, int64_t n_cells, vae_stream_t stream) {
-    if (!src || !dst) return vae_set_error("vae_expand_stimuli", "null pointer");
-    if (kind != 0 && kind != 1) return vae_set_error("vae_expand_stimuli", "kind must be 0 (bytes) or 1 (bit planes)");
-    if (n_cells < 0 || n_cells % 8) return vae_set_error("vae_expand_stimuli", "the number of cells must be a multiple of 8");
-    if (n_cells == 0) return 0;
-    // the address the device uses for the source: device memory as is, pinned host memory through its mapping; anything else
-    // (pageable host memory) is refused - a kernel must not dereference it
-    hipPointerAttribute_t at; memset(&at, 0, sizeof(at));
-    if (hipPointerGetAttributes(&at, src) != hipSuccess) { (void)hipGetLastError(); return vae_set_error("vae_expand_stimuli", "the source is neither device nor pinned host memory"); }
-    const void* dsrc = nullptr;
-    if (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged) dsrc = src;
-    else if (at.type == hipMemoryTypeHost && at.devicePointer) dsrc = at.devicePointer;
-    else return vae_set_error("vae_expand_stimuli", "the source is neither device nor pinned host memory");
-    if ((reinterpret_cast<uintptr_t>(dsrc) & 3) || (reinterpret_cast<uintptr_t>(dst) & 15)) return vae_set_error("vae_expand_stimuli", "source must be 4-byte, destination 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    if (kind == 0) {
-        const long n4 = n_cells / 4;
-        hipLaunchKernelGGL(expand_bytes_kernel, dim3((unsigned)std::min<long>((n4 + 255) / 256, 2048)), dim3(256), 0, st, reinterpret_cast<const uint32_t*>(dsrc), dst, n4);
-    } else {
-        const long nb = n_cells / 8;
-        hipLaunchKernelGGL(expand_bits_kernel, dim3((unsigned)std::min<long>((nb + 255) / 256, 2048)), dim3(256), 0, st, reinterpret_cast<const uint8_t*>(dsrc), dst, nb);
-    }
-    LAUNCH_CHECK("expand_stimuli_kernel");
-    return 0;
-}
-
-
 // ---------------------------------------------------------------------------
+// the opening of every entry point that runs a batch through the context
+static int check_ctx_batch(const char* what, const vae_ctx* c, int B) {
+    if (!c) return vae_set_error(what, "null ctx");
+    if (B < 1 || B > c->maxB) return vae_set_error(what, "batch exceeds the context's max_batch");
+    return 0;
+}
 extern "C" int vae_forward(vae_ctx* c, const float* x, int B, const float* params, float* bn_running, int64_t* nbt,
                            const float* eps, uint64_t seed, int train, float* xhat, float* mu, float* lv, float* z, vae_stream_t stream) {
-    if (!c) return vae_set_error("vae_forward", "null ctx");
-    if (B < 1 || B > c->maxB) return vae_set_error("vae_forward", "batch exceeds the context's max_batch");
+    if (check_ctx_batch("vae_forward", c, B)) return -1;
     if (!x || !params || !xhat || !mu || !lv || !z) return vae_set_error("vae_forward", "null tensor pointer");
     if (c->kl_kind == VAE_KL_TC && B > TC_MAX_B) return vae_set_error("vae_forward", "the total-correlation objective (VAE_KL_TC) takes batches of at most 4096");
     hipStream_t st = (hipStream_t)stream;
@@ -376,8 +306,7 @@ extern "C" int vae_forward(vae_ctx* c, const float* x, int B, const float* param
 
 extern "C" int vae_decode(vae_ctx* c, const float* z, int B, const float* params, float* bn_running, int64_t* nbt, int train,
                           float* xhat, vae_stream_t stream) {
-    if (!c) return vae_set_error("vae_decode", "null ctx");
-    if (B < 1 || B > c->maxB) return vae_set_error("vae_decode", "batch exceeds the context's max_batch");
+    if (check_ctx_batch("vae_decode", c, B)) return -1;
     if (!z || !params || !xhat) return vae_set_error("vae_decode", "null tensor pointer");
     hipStream_t st = (hipStream_t)stream;
     // what vae_backward_ex needs of a decode-only pass: its BatchNorm mode, z, xhat, the gradient scale; vae_backward refuses it
@@ -392,8 +321,7 @@ extern "C" int vae_decode(vae_ctx* c, const float* z, int B, const float* params
 
 extern "C" int vae_encode(vae_ctx* c, const float* x, int B, const float* params, float* bn_running, int64_t* nbt,
                           const float* eps, uint64_t seed, int train, float* mu, float* lv, float* z, vae_stream_t stream) {
-    if (!c) return vae_set_error("vae_encode", "null ctx");
-    if (B < 1 || B > c->maxB) return vae_set_error("vae_encode", "batch exceeds the context's max_batch");
+    if (check_ctx_batch("vae_encode", c, B)) return -1;
     if (!x || !params || !mu || !lv || !z) return vae_set_error("vae_encode", "null tensor pointer");
     hipStream_t st = (hipStream_t)stream;
     if (begin_forward(c, FwdRecord::ENCODE, B, train, st)) return -1;
@@ -410,7 +338,7 @@ extern "C" int vae_log_likelihood(vae_ctx* c, const float* x, int B, const float
                                   const float* eps, uint64_t seed, double* log_w, double* ll, double* elbo, vae_stream_t stream) {
     if (!c) return vae_set_error("vae_log_likelihood", "null ctx");
     if (!x || !params || !bn_running || !ll || !elbo) return vae_set_error("vae_log_likelihood", "null tensor pointer");
-    if (B < 1 || B > c->maxB) return vae_set_error("vae_log_likelihood", "batch exceeds the context's max_batch");
+    if (check_ctx_batch("vae_log_likelihood", c, B)) return -1;   // (the batch: here the tensors are checked in front of it)
     if (K < 1 || chunk < 1) return vae_set_error("vae_log_likelihood", "num_samples and chunk must be >= 1");
     if ((int64_t)chunk * B > c->maxB) return vae_set_error("vae_log_likelihood", "chunk * batch exceeds the context's max_batch");
     hipStream_t st = (hipStream_t)stream;
@@ -445,8 +373,7 @@ extern "C" int vae_log_likelihood(vae_ctx* c, const float* x, int B, const float
         la.seed = (unsigned long long)seed;
         {
             ProfScope ps(c, "iw_latent", 4.0 * R * L * (eps ? 2 : 1) + 8.0 * R, 0, st);
-            hipLaunchKernelGGL(iw_latent_kernel, dim3((R + 255) / 256), dim3(256), 0, st, la);
-            LAUNCH_CHECK("iw_latent_kernel");
+            if (launch("iw_latent_kernel", iw_latent_kernel, dim3((R + 255) / 256), dim3(256), 0, st, la)) return -1;
         }
         c->ps_part = c->ll_part; c->ps_tb = B; c->ps_ntile = 0;
         rc = VAE_DISPATCH(c->dtype, decode_impl, (c, zc, R, params, bnr, nullptr, 0, x, nullptr, st));
@@ -454,14 +381,11 @@ extern "C" int vae_log_likelihood(vae_ctx* c, const float* x, int B, const float
         if (rc) return rc;
         if (c->ps_ntile < 1) return vae_set_error("vae_log_likelihood", "the output conv did not run in its per-sample mode");
         ProfScope ps(c, "loglik_rows", 8.0 * R * (c->ps_ntile + 3), 0, st);
-        hipLaunchKernelGGL(loglik_rows_kernel, dim3((R + 255) / 256), dim3(256), 0, st, c->ll_part, c->ps_ntile, c->ll_lat, R,
-                           (long)k0 * B, cst, lpx, lw);
-        LAUNCH_CHECK("loglik_rows_kernel");
+        if (launch("loglik_rows_kernel", loglik_rows_kernel, dim3((R + 255) / 256), dim3(256), 0, st, c->ll_part, c->ps_ntile, c->ll_lat, R,
+                   (long)k0 * B, cst, lpx, lw)) return -1;
     }
     ProfScope ps(c, "loglik_final", 16.0 * kb, 0, st);
-    hipLaunchKernelGGL(loglik_final_kernel, dim3((B + 255) / 256), dim3(256), 0, st, lpx, lw, mu, lv, K, B, L, ll, elbo);
-    LAUNCH_CHECK("loglik_final_kernel");
-    return 0;
+    return launch("loglik_final_kernel", loglik_final_kernel, dim3((B + 255) / 256), dim3(256), 0, st, lpx, lw, mu, lv, K, B, L, ll, elbo);
 }
 
 extern "C" int vae_set_recon_loss(vae_ctx* c, int kind) {
@@ -491,10 +415,8 @@ static int enqueue_kl_shape(const float* mu, const float* lv, int B, int L, int 
     HIP_CHECK_RET(hipMemsetAsync(ticket, 0, 16, st));
     KlShapeArgs a; a.mu = mu; a.lv = lv; a.kl_d = kl_d; a.factor = factor; a.scal = scal; a.ticket = ticket; a.B = B; a.L = L; a.kind = kind; a.param = param;
     const bool vec = L % 4 == 0 && !(((uintptr_t)mu | (uintptr_t)lv) & 15);
-    if (vec) hipLaunchKernelGGL(kl_shape_kernel<4>, dim3(L / 4), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(kl_shape_kernel<1>, dim3(L), dim3(256), 0, st, a);
-    LAUNCH_CHECK("kl_shape_kernel");
-    return 0;
+    if (vec) return launch("kl_shape_kernel", kl_shape_kernel<4>, dim3(L / 4), dim3(256), 0, st, a);
+    return launch("kl_shape_kernel", kl_shape_kernel<1>, dim3(L), dim3(256), 0, st, a);
 }
 int launch_kl_shape(vae_ctx* c, hipStream_t st) {
     if (!c->kl_ws) {
@@ -538,33 +460,26 @@ static int enqueue_tc(vae_ctx* c, const float* mu, const float* lv, const float*
     const unsigned tiles = (unsigned)((B + TC_TILE - 1) / TC_TILE);
     {
         ProfScope ps(c, "tc_prep", 24.0 * bl, 0, st);
-        hipLaunchKernelGGL(tc_prep_kernel, dim3((B + 3) / 4), dim3(256), 0, st, mu, lv, eps, B, L, w.z, w.hw, w.c2, w.cj);
-        LAUNCH_CHECK("tc_prep_kernel");
+        if (launch("tc_prep_kernel", tc_prep_kernel, dim3((B + 3) / 4), dim3(256), 0, st, mu, lv, eps, B, L, w.z, w.hw, w.c2, w.cj)) return -1;
     }
     {
         ProfScope ps(c, "tc_pair", 12.0 * bl + 4.0 * bb, 3.0 * bb * L, st);
-        hipLaunchKernelGGL(tc_pair_kernel, dim3(tiles, tiles), dim3(256), 0, st, w.z, mu, w.hw, w.cj, B, L, w.A);
-        LAUNCH_CHECK("tc_pair_kernel");
+        if (launch("tc_pair_kernel", tc_pair_kernel, dim3(tiles, tiles), dim3(256), 0, st, w.z, mu, w.hw, w.cj, B, L, w.A)) return -1;
     }
     {
         ProfScope ps(c, "tc_row", 4.0 * bb, 0, st);
-        hipLaunchKernelGGL(tc_row_kernel, dim3((B + 3) / 4), dim3(256), 0, st, w.A, B, w.lse);
-        LAUNCH_CHECK("tc_row_kernel");
+        if (launch("tc_row_kernel", tc_row_kernel, dim3((B + 3) / 4), dim3(256), 0, st, w.A, B, w.lse)) return -1;
     }
     {
         ProfScope ps(c, "tc_query", 24.0 * bl + 4.0 * bb, (a.grad ? 14.0 : 5.0) * bb * L, st);
-        hipLaunchKernelGGL(tc_query_kernel, dim3(w.npart), dim3(256), 0, st, a);
-        LAUNCH_CHECK("tc_query_kernel");
+        if (launch("tc_query_kernel", tc_query_kernel, dim3(w.npart), dim3(256), 0, st, a)) return -1;
     }
     if (a.grad) {
         ProfScope ps(c, "tc_comp", 36.0 * bl + 4.0 * bb, 12.0 * bb * L, st);
-        hipLaunchKernelGGL(tc_comp_kernel, dim3(w.npart), dim3(256), 0, st, a);
-        LAUNCH_CHECK("tc_comp_kernel");
+        if (launch("tc_comp_kernel", tc_comp_kernel, dim3(w.npart), dim3(256), 0, st, a)) return -1;
     }
     ProfScope ps(c, "tc_final", 4.0 * B + 8.0 * w.npart, 0, st);
-    hipLaunchKernelGGL(tc_final_kernel, dim3(1), dim3(256), 0, st, w.lse, w.part, w.npart, B, L, tc_out, scal, tc_weight);
-    LAUNCH_CHECK("tc_final_kernel");
-    return 0;
+    return launch("tc_final_kernel", tc_final_kernel, dim3(1), dim3(256), 0, st, w.lse, w.part, w.npart, B, L, tc_out, scal, tc_weight);
 }
 extern "C" int vae_total_correlation(const float* mu, const float* lv, const float* eps, int B, int L, double* tc, float* g_mu,
                                      float* g_lv, vae_stream_t stream) {
@@ -572,14 +487,10 @@ extern "C" int vae_total_correlation(const float* mu, const float* lv, const flo
     if (B < 1 || B > TC_MAX_B) return vae_set_error("vae_total_correlation", "batch must be in 1..4096");
     if (L < 1 || L > 4096) return vae_set_error("vae_total_correlation", "latent_dim must be in 1..4096");
     hipStream_t st = (hipStream_t)stream;
-    void* ws = nullptr;
-    HIP_CHECK_RET(hipMallocAsync(&ws, tc_carve(nullptr, B, L, nullptr), st));
-    TcWork w; tc_carve(ws, B, L, &w);
-    const int rc = enqueue_tc(nullptr, mu, lv, eps, B, L, w, tc, g_mu, g_lv, L, nullptr, 0.0, st);
-    const hipError_t fe = hipFreeAsync(ws, st);
-    if (rc) return rc;
-    if (fe != hipSuccess) return vae_set_error("hipFreeAsync", hipGetErrorString(fe));
-    return 0;
+    return with_stream_scratch(tc_carve(nullptr, B, L, nullptr), st, [&](char* base) -> int {
+        TcWork w; tc_carve(base, B, L, &w);
+        return enqueue_tc(nullptr, mu, lv, eps, B, L, w, tc, g_mu, g_lv, L, nullptr, 0.0, st);
+    });
 }
 // The context's work space: the gradient [B][2L] (g_mu | g_log_var) in front, the kernels' pieces behind it; sized for the largest
 // batch a forward has asked for so far (a larger one frees and allocates again, behind a device synchronisation).
@@ -635,10 +546,8 @@ extern "C" int vae_last_total_correlation(vae_ctx* c, double* out, vae_stream_t 
 
 // the ELBO scalars {loss, reconstruction, -KL} of the last forward from the context's accumulators (a shaped KL objective: after join_kl)
 int launch_loss_finalize(vae_ctx* c, float* out3, float kld_weight, hipStream_t st) {
-    hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, st, c->accum, out3, 1.0 / ((double)c->fwd.B * c->H * c->H),
-                       1.0 / (double)c->fwd.B, kld_weight, STAT_R, c->kl_shaped());
-    LAUNCH_CHECK("loss_finalize_kernel");
-    return 0;
+    return launch("loss_finalize_kernel", loss_finalize_kernel, dim3(1), dim3(64), 0, st, c->accum, out3, 1.0 / ((double)c->fwd.B * c->H * c->H),
+                  1.0 / (double)c->fwd.B, kld_weight, STAT_R, c->kl_shaped());
 }
 
 extern "C" int vae_loss(vae_ctx* c, float kld_weight, float* out3, vae_stream_t stream) {
@@ -680,41 +589,25 @@ static int elbo_generic(const char* what, const float* xhat, const float* target
     double* acc = g_generic_ring[dev] + 4 * (g_generic_next[dev]++ % kGenericSlots);
     HIP_CHECK_RET(hipMemsetAsync(acc, 0, 4 * sizeof(double), st));
     const dim3 grid((unsigned)std::min<long>((n + 255) / 256, 2048));
-    if (recon == VAE_RECON_MSE) {
-        hipLaunchKernelGGL(mse_kernel, grid, dim3(256), 0, st, xhat, target, g_xhat, acc, (long)n, (float)(2.0 / (double)n));
-        LAUNCH_CHECK("mse_kernel");
-    } else {
-        hipLaunchKernelGGL(bce_kernel, grid, dim3(256), 0, st, xhat, target, g_xhat, acc, (long)n, (float)(1.0 / (double)n));
-        LAUNCH_CHECK("bce_kernel");
-    }
-    if (kl_kind == VAE_KL_PLAIN) {
-        hipLaunchKernelGGL(kld_only_kernel, dim3((B * L + 255) / 256), dim3(256), 0, st, mu, lv, acc, B * L, kld_weight / (float)B, g_mu, g_lv);
-        LAUNCH_CHECK("kld_only_kernel");
-        hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, st, acc, out3, 1.0 / (double)n, 1.0 / (double)B, kld_weight, 1);
-        LAUNCH_CHECK("loss_finalize_kernel");
-        return 0;
-    }
-    // shaped objective: the reduction in front (its work space from the stream-ordered allocator: kl_d | scalars | factor | ticket block)
-    void* ws = nullptr;
-    const size_t fac_off = (size_t)L * 8 + 16, tk_off = (fac_off + (size_t)L * 4 + 15) / 16 * 16;
-    HIP_CHECK_RET(hipMallocAsync(&ws, tk_off + 16, st));
-    char* base = static_cast<char*>(ws);
-    auto run = [&]() -> int {
-        const float* factor = reinterpret_cast<const float*>(base + fac_off);
-        const double* scal = reinterpret_cast<const double*>(base + (size_t)L * 8);
-        if (enqueue_kl_shape(mu, lv, B, L, kl_kind, kl_param, reinterpret_cast<unsigned long long*>(base), const_cast<double*>(scal),
-                             const_cast<float*>(factor), reinterpret_cast<unsigned*>(base + tk_off), st)) return -1;
-        hipLaunchKernelGGL(kld_only_kernel, dim3((B * L + 255) / 256), dim3(256), 0, st, mu, lv, acc, B * L, kld_weight / (float)B, g_mu, g_lv, factor, L);
-        LAUNCH_CHECK("kld_only_kernel");
-        hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, st, acc, out3, 1.0 / (double)n, 1.0 / (double)B, kld_weight, 1, scal);
-        LAUNCH_CHECK("loss_finalize_kernel");
-        return 0;
+    const int rc = recon == VAE_RECON_MSE ? launch("mse_kernel", mse_kernel, grid, dim3(256), 0, st, xhat, target, g_xhat, acc, (long)n, (float)(2.0 / (double)n))
+                                           : launch("bce_kernel", bce_kernel, grid, dim3(256), 0, st, xhat, target, g_xhat, acc, (long)n, (float)(1.0 / (double)n));
+    if (rc) return -1;
+    // the KL term and the scalars; factor / scal null and FL 1: the plain objective
+    const auto tail = [&](const float* factor, int FL, const double* scal) -> int {
+        if (launch("kld_only_kernel", kld_only_kernel, dim3((B * L + 255) / 256), dim3(256), 0, st, mu, lv, acc, B * L, kld_weight / (float)B, g_mu, g_lv,
+                   factor, FL)) return -1;
+        return launch("loss_finalize_kernel", loss_finalize_kernel, dim3(1), dim3(64), 0, st, acc, out3, 1.0 / (double)n, 1.0 / (double)B, kld_weight, 1, scal);
     };
-    const int rc = run();
-    const hipError_t fe = hipFreeAsync(ws, st);
-    if (rc) return rc;
-    if (fe != hipSuccess) return vae_set_error("hipFreeAsync", hipGetErrorString(fe));
-    return 0;
+    if (kl_kind == VAE_KL_PLAIN) return tail(nullptr, 1, nullptr);
+    // shaped objective: the reduction in front (its work space from the stream-ordered allocator: kl_d | scalars | factor | ticket block)
+    const size_t fac_off = (size_t)L * 8 + 16, tk_off = (fac_off + (size_t)L * 4 + 15) / 16 * 16;
+    return with_stream_scratch(tk_off + 16, st, [&](char* base) -> int {
+        float* factor = reinterpret_cast<float*>(base + fac_off);
+        double* scal = reinterpret_cast<double*>(base + (size_t)L * 8);
+        if (enqueue_kl_shape(mu, lv, B, L, kl_kind, kl_param, reinterpret_cast<unsigned long long*>(base), scal, factor,
+                             reinterpret_cast<unsigned*>(base + tk_off), st)) return -1;
+        return tail(factor, L, scal);
+    });
 }
 extern "C" int vae_elbo_generic_ex(const float* xhat, const float* target, const float* mu, const float* lv, int64_t n, int B, int L,
                                    float kld_weight, int recon, float* out3, float* g_xhat, float* g_mu, float* g_lv, vae_stream_t stream) {
@@ -728,146 +621,6 @@ extern "C" int vae_elbo_generic_kl(const float* xhat, const float* target, const
 extern "C" int vae_elbo_generic(const float* xhat, const float* target, const float* mu, const float* lv, int64_t n, int B, int L,
                                 float kld_weight, float* out3, float* g_xhat, float* g_mu, float* g_lv, vae_stream_t stream) {
     return vae_elbo_generic_ex(xhat, target, mu, lv, n, B, L, kld_weight, VAE_RECON_BCE, out3, g_xhat, g_mu, g_lv, stream);
-}
-
-// Latent diagnostics (latent_stats.cuh).  Launches: prep (tables, z), joint and dims pairwise kernels over split component ranges,
-// two merges, the per-dimension moments, the scalar combine.  Work space from the stream-ordered allocator, freed on the stream.
-// The split counts depend on (n, L, draws) only, so a given shape always reduces in the same order.
-extern "C" int vae_latent_stats(const float* mu, const float* lv, int64_t n, int L, int S, const float* eps, uint64_t seed,
-                                double* log_qz, double* log_qz_dims, double* per_dim, double* scalars, vae_stream_t stream) {
-    if (!mu || !lv || !log_qz || !log_qz_dims || !per_dim || !scalars) return vae_set_error("vae_latent_stats", "null tensor pointer");
-    if (n < 1 || n > (int64_t)1 << 30) return vae_set_error("vae_latent_stats", "n must be in [1, 2^30]");
-    if (L < 1 || L > 4096) return vae_set_error("vae_latent_stats", "latent_dim must be in [1, 4096]");
-    if (S < 1) return vae_set_error("vae_latent_stats", "draws must be >= 1");
-    const long N = (long)n, SN = (long)S * N;
-    if (SN > ((long)1 << 40) / L) return vae_set_error("vae_latent_stats", "draws * n * latent_dim too large");
-    hipStream_t st = (hipStream_t)stream;
-    // split of the component range: enough waves for the 256 CUs, at least 256 components per split, at most 64 splits
-    auto splits = [&](long waves, long target, int tile, int& jper) {
-        long ns = std::max<long>(1, std::min<long>({(target + waves - 1) / waves, (N + 255) / 256, 64}));
-        jper = (int)(((N + ns - 1) / ns + tile - 1) / tile * tile);
-        return (int)((N + jper - 1) / jper);
-    };
-    const long jblocks = (SN + 256 * LS_QR - 1) / (256 * LS_QR);
-    int jper_j = 0;
-    const int nsj = splits(jblocks * 4, 2048, LS_JT, jper_j);
-    const int DB = std::min(L, LS_DB), QG = 256 / DB, ndt = (L + DB - 1) / DB;
-    const long dblocks = (long)ndt * ((SN + (long)QG * LS_QR - 1) / ((long)QG * LS_QR));
-    int jper_d = 0;
-    const int nsd = splits(dblocks * 4, 4096, LS_JD, jper_d);
-    if (jblocks > INT32_MAX || dblocks > INT32_MAX) return vae_set_error("vae_latent_stats", "grid too large");
-    const size_t nl = (size_t)N * L, snl = (size_t)SN * L;
-    size_t off[8], tot = 0;
-    const size_t sz[7] = {snl * 4, nl * 8, nl * 4, (size_t)N * 4, (size_t)nsj * SN * 8, (size_t)nsd * snl * 8, (size_t)4 * L * 8};
-    for (int k = 0; k < 7; ++k) { off[k] = tot; tot += (sz[k] + 255) / 256 * 256; }
-    void* ws = nullptr;
-    HIP_CHECK_RET(hipMallocAsync(&ws, tot, st));
-    char* base = static_cast<char*>(ws);
-    float* z = reinterpret_cast<float*>(base + off[0]);
-    float2* mh = reinterpret_cast<float2*>(base + off[1]);
-    float* c2 = reinterpret_cast<float*>(base + off[2]);
-    float* cj = reinterpret_cast<float*>(base + off[3]);
-    float2* pj = reinterpret_cast<float2*>(base + off[4]);
-    float2* pd = reinterpret_cast<float2*>(base + off[5]);
-    double* dstat = reinterpret_cast<double*>(base + off[6]);
-    const double lnN = log((double)N);
-    auto run = [&]() -> int {
-        hipLaunchKernelGGL(lstat_prep_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, mu, lv, eps, (unsigned long long)seed,
-                           (int)N, L, S, z, mh, c2, cj);
-        LAUNCH_CHECK("lstat_prep_kernel");
-        hipLaunchKernelGGL(lstat_joint_kernel, dim3((unsigned)jblocks, nsj), dim3(256), 0, st, z, mh, cj, SN, (int)N, L, jper_j, pj);
-        LAUNCH_CHECK("lstat_joint_kernel");
-        hipLaunchKernelGGL(lstat_dims_kernel, dim3((unsigned)dblocks, nsd), dim3(256), 0, st, z, mh, c2, SN, (int)N, L, DB, ndt, jper_d, pd);
-        LAUNCH_CHECK("lstat_dims_kernel");
-        hipLaunchKernelGGL(lstat_merge_kernel, dim3((unsigned)std::min<long>((SN + 255) / 256, 4096)), dim3(256), 0, st, pj, nsj, SN, lnN,
-                           log_qz);
-        LAUNCH_CHECK("lstat_merge_kernel");
-        hipLaunchKernelGGL(lstat_merge_kernel, dim3((unsigned)std::min<long>((long)(snl + 255) / 256, 8192)), dim3(256), 0, st, pd, nsd,
-                           (long)snl, lnN, log_qz_dims);
-        LAUNCH_CHECK("lstat_merge_kernel");
-        hipLaunchKernelGGL(lstat_moments_kernel, dim3(L), dim3(256), 0, st, mu, lv, log_qz_dims, (int)N, SN, L, per_dim, dstat);
-        LAUNCH_CHECK("lstat_moments_kernel");
-        hipLaunchKernelGGL(lstat_final_kernel, dim3(1), dim3(256), 0, st, log_qz, SN, dstat, L, scalars);
-        LAUNCH_CHECK("lstat_final_kernel");
-        return 0;
-    };
-    const int rc = run();
-    const hipError_t fe = hipFreeAsync(ws, st);
-    if (rc) return rc;
-    if (fe != hipSuccess) return vae_set_error("hipFreeAsync", hipGetErrorString(fe));
-    return 0;
-}
-
-// Note-level reconstruction metrics (recon_metrics.cuh).  Two launches: the pass over the cells, one workgroup per (roll, chunk), and
-// the fold of chunks into rolls and of rolls into the totals, one wave per output field.  The per-chunk ranges (and, for rolls longer than one
-// chunk, the per-chunk sums and counts) go through the stream-ordered allocator; nothing is read back.
-template <int T>
-static int recon_metrics_launch(std::integral_constant<int, T>, unsigned grid, hipStream_t st, const float* xhat, const float* target,
-                                long roll_len, long nchunks, const RmThresholds& th, float tt, double* ps, long long* pc, float* pr) {
-    hipLaunchKernelGGL(recon_metrics_kernel<T>, dim3(grid), dim3(RM_THREADS), 0, st, xhat, target, roll_len, nchunks, th, tt, ps, pc, pr);
-    LAUNCH_CHECK("recon_metrics_kernel");
-    return 0;
-}
-extern "C" int vae_recon_metrics(const float* xhat, const float* target, int64_t rolls, int64_t roll_len, const float* thresholds,
-                                 int n_thresholds, float target_threshold, double* roll_sums, int64_t* roll_counts, double* totals,
-                                 int64_t* total_counts, int accumulate, vae_stream_t stream) {
-    const char* what = "vae_recon_metrics";
-    if (!thresholds || !totals || !total_counts) return vae_set_error(what, "null pointer (thresholds, totals, total_counts)");
-    if (n_thresholds < 1 || n_thresholds > RM_MAX_T) return vae_set_error(what, "n_thresholds must be in 1..8");
-    RmThresholds th{};
-    for (int k = 0; k < n_thresholds; ++k) {
-        if (!std::isfinite(thresholds[k])) return vae_set_error(what, "thresholds must be finite");
-        th.t[k] = thresholds[k];
-    }
-    if (!std::isfinite(target_threshold)) return vae_set_error(what, "target_threshold must be finite");
-    if (rolls < 0) return vae_set_error(what, "rolls must be >= 0");
-    if (roll_len < 1) return vae_set_error(what, "roll_len must be >= 1");
-    if (accumulate != 0 && accumulate != 1) return vae_set_error(what, "accumulate must be 0 or 1");
-    hipStream_t st = (hipStream_t)stream;
-    const int ncnt = 1 + 2 * n_thresholds;
-    if (rolls == 0) {
-        if (!accumulate) {
-            HIP_CHECK_RET(hipMemsetAsync(totals, 0, 8 * sizeof(double), st));
-            HIP_CHECK_RET(hipMemsetAsync(total_counts, 0, ncnt * sizeof(int64_t), st));
-        }
-        return 0;
-    }
-    if (!xhat || !target || !roll_sums || !roll_counts) return vae_set_error(what, "null pointer (xhat, target, roll_sums, roll_counts)");
-    if ((reinterpret_cast<uintptr_t>(xhat) | reinterpret_cast<uintptr_t>(target)) & 3) return vae_set_error(what, "xhat and target must be 4-byte aligned");
-    const int64_t nchunks = (roll_len - 1) / RM_CHUNK + 1;
-    if (rolls > INT32_MAX / nchunks) return vae_set_error(what, "rolls * ceil(roll_len / 4096) must stay below 2^31");
-    if (roll_len > ((int64_t)1 << 52) / rolls) return vae_set_error(what, "rolls * roll_len must stay below 2^52");
-    const size_t np = (size_t)(rolls * nchunks);
-    const size_t rng_bytes = (np * 4 * sizeof(float) + 255) / 256 * 256, sum_bytes = (np * 3 * sizeof(double) + 255) / 256 * 256;
-    const bool split = nchunks > 1;
-    void* ws = nullptr;
-    HIP_CHECK_RET(hipMallocAsync(&ws, rng_bytes + (split ? sum_bytes + np * ncnt * sizeof(int64_t) : 0), st));
-    char* base = static_cast<char*>(ws);
-    float* pr = reinterpret_cast<float*>(base);
-    double* ps = split ? reinterpret_cast<double*>(base + rng_bytes) : roll_sums;
-    long long* pc = split ? reinterpret_cast<long long*>(base + rng_bytes + sum_bytes) : reinterpret_cast<long long*>(roll_counts);
-    auto run = [&]() -> int {
-        auto go = [&](auto t) {
-            return recon_metrics_launch(t, (unsigned)np, st, xhat, target, (long)roll_len, (long)nchunks, th, target_threshold, ps, pc, pr);
-        };
-        int rc = 0;   // the threshold count is a template argument: the counters stay in registers
-        switch (n_thresholds) {
-#define RM_CASE(T) case T: rc = go(std::integral_constant<int, T>{}); break;
-            RM_CASE(1) RM_CASE(2) RM_CASE(3) RM_CASE(4) RM_CASE(5) RM_CASE(6) RM_CASE(7) RM_CASE(8)
-#undef RM_CASE
-        }
-        if (rc) return rc;
-        hipLaunchKernelGGL(recon_metrics_fold_kernel, dim3(1 + (3 + ncnt + 3) / 4), dim3(RM_THREADS), 0, st, (long)rolls, (long)nchunks, ncnt,
-                           (double)rolls * (double)roll_len, ps, pc, pr, roll_sums, reinterpret_cast<long long*>(roll_counts), totals,
-                           reinterpret_cast<long long*>(total_counts), accumulate);
-        LAUNCH_CHECK("recon_metrics_fold_kernel");
-        return 0;
-    };
-    const int rc = run();
-    const hipError_t fe = hipFreeAsync(ws, st);
-    if (rc) return rc;
-    if (fe != hipSuccess) return vae_set_error("hipFreeAsync", hipGetErrorString(fe));
-    return 0;
 }
 
 // A non-blocking stream owned by the context, ordered after everything enqueued on `stream` so far.  Work the caller
@@ -907,27 +660,36 @@ extern "C" int vae_backward(vae_ctx* c, const float* x, const float* params, flo
     return vae_backward_part(c, x, params, grads, g_xhat, gscale, g_mu, g_lv, g_z, g_pre, kld_weight, add_kl, 0, stream);
 }
 
+// The arguments of the AdamW kernels and their grid.  Every scalar of torch's single-tensor update is formed in double from the Python
+// floats and reaches the element-wise kernel as one float: beta, 1 - beta, 1 - lr * weight_decay, eps, and the two that depend on the
+// step count, lr / (1 - beta1^t) and 1 / sqrt(1 - beta2^t): zero here, filled by vae_adamw_step from its host step, taken from the
+// device record by the clipped update.
+static dim3 adam_args(AdamArgs& a, float* params, const float* grads, float* m, float* v, int ngroups, const int64_t* offsets,
+                      const int64_t* sizes, const double* lrs, const double* beta1s, double beta2, double eps, double weight_decay,
+                      float grad_scale, int step) {
+    a.p = params; a.g = grads; a.m = m; a.v = v; a.ngrp = ngroups; a.beta2 = (float)beta2; a.omb2 = (float)(1.0 - beta2); a.eps = (float)eps;
+    a.grad_scale = grad_scale; a.step = step;
+    long nmax = 0;
+    for (int i = 0; i < ngroups; ++i) {
+        a.grp[i].off = offsets[i]; a.grp[i].n = sizes[i]; nmax = std::max<long>(nmax, sizes[i]);
+        a.grp[i].beta1 = (float)beta1s[i]; a.grp[i].omb1 = (float)(1.0 - beta1s[i]); a.grp[i].decay = (float)(1.0 - lrs[i] * weight_decay);
+        a.grp[i].step_size = 0.f; a.grp[i].inv_sqrt_bc2 = 0.f;
+    }
+    return dim3((unsigned)std::min<long>((nmax / 4 + 255) / 256 + 1, 2048), ngroups);
+}
 extern "C" int vae_adamw_step(float* params, const float* grads, float* m, float* v, int ngroups, const int64_t* offsets,
                               const int64_t* sizes, const double* lrs, const double* beta1s, double beta2, double eps, double weight_decay,
                               float grad_scale, int step, vae_stream_t stream) {
     if (ngroups < 1 || ngroups > 2) return vae_set_error("vae_adamw_step", "1 or 2 groups");
     if (step < 1) return vae_set_error("vae_adamw_step", "step is 1-based");
     AdamArgs a;
-    // every scalar of torch's single-tensor update is formed in double from the Python floats and reaches the element-wise kernel as
-    // one float: beta, 1 - beta, 1 - lr * weight_decay, lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t), eps
-    a.p = params; a.g = grads; a.m = m; a.v = v; a.ngrp = ngroups; a.beta2 = (float)beta2; a.omb2 = (float)(1.0 - beta2); a.eps = (float)eps;
-    a.grad_scale = grad_scale; a.step = step;
-    long nmax = 0;
+    const dim3 grid = adam_args(a, params, grads, m, v, ngroups, offsets, sizes, lrs, beta1s, beta2, eps, weight_decay, grad_scale, step);
     const double bc2 = 1.0 - pow(beta2, (double)step);
     for (int i = 0; i < ngroups; ++i) {
-        a.grp[i].off = offsets[i]; a.grp[i].n = sizes[i]; nmax = std::max<long>(nmax, sizes[i]);
-        a.grp[i].beta1 = (float)beta1s[i]; a.grp[i].omb1 = (float)(1.0 - beta1s[i]); a.grp[i].decay = (float)(1.0 - lrs[i] * weight_decay);
         const double bc1 = 1.0 - pow(beta1s[i], (double)step);   // torch.optim.AdamW: bias corrections with the CURRENT (cycled) beta1
         a.grp[i].step_size = (float)(lrs[i] / bc1); a.grp[i].inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
     }
-    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)std::min<long>((nmax / 4 + 255) / 256 + 1, 2048), ngroups), dim3(256), 0, (hipStream_t)stream, a);
-    LAUNCH_CHECK("adamw_kernel");
-    return 0;
+    return launch("adamw_kernel", adamw_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
 }
 
 // Gradient clipping / non-finite skipping (grad_clip.cuh).  The device-side arguments of the clipped update.
@@ -935,11 +697,15 @@ struct ClipArgs {
     double max_grad_norm; int skip_nonfinite;
     int64_t* step; double* norm_out; int64_t* skipped; void* scratch;
 };
-static int check_clip_args(const char* what, int ngroups, const int64_t* offsets, const int64_t* sizes, const ClipArgs& k) {
+static int check_groups(const char* what, int ngroups, const int64_t* offsets, const int64_t* sizes) {
     if (ngroups < 1 || ngroups > 2) return vae_set_error(what, "1 or 2 groups");
     if (!offsets || !sizes) return vae_set_error(what, "null offsets / sizes");
     for (int i = 0; i < ngroups; ++i)
         if (offsets[i] < 0 || sizes[i] < 1) return vae_set_error(what, "empty or negative range");
+    return 0;
+}
+static int check_clip_args(const char* what, int ngroups, const int64_t* offsets, const int64_t* sizes, const ClipArgs& k) {
+    if (check_groups(what, ngroups, offsets, sizes)) return -1;
     if (k.max_grad_norm != k.max_grad_norm) return vae_set_error(what, "max_grad_norm is NaN");
     if (!k.step || !k.norm_out || !k.skipped || !k.scratch) return vae_set_error(what, "null device pointer (step, norm_out, skipped, scratch)");
     if ((uintptr_t)k.scratch % 16) return vae_set_error(what, "scratch must be 16-byte aligned");
@@ -951,45 +717,29 @@ static int launch_grad_norm(const float* grads, int ngroups, const int64_t* offs
     GradSumsqArgs s;
     s.g = grads; s.grad_scale = grad_scale; s.partial = static_cast<double*>(k.scratch);
     for (int i = 0; i < ngroups; ++i) { s.off[i] = offsets[i]; s.n[i] = sizes[i]; }
-    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(GCLIP_BLOCKS, ngroups), dim3(256), 0, st, s);
-    LAUNCH_CHECK("grad_sumsq_kernel");
+    if (launch("grad_sumsq_kernel", grad_sumsq_kernel, dim3(GCLIP_BLOCKS, ngroups), dim3(256), 0, st, s)) return -1;
     GradClipArgs f = {};
     f.partial = s.partial; f.ngrp = ngroups; f.max_norm = k.max_grad_norm; f.skip = k.skip_nonfinite ? 1 : 0;
     f.step = clip ? reinterpret_cast<long long*>(k.step) : nullptr; f.skipped = reinterpret_cast<long long*>(k.skipped);
     f.norm_out = k.norm_out; f.beta2 = beta2;
     for (int i = 0; i < ngroups && clip; ++i) { f.lr[i] = lrs[i]; f.beta1[i] = beta1s[i]; }
     f.rec = reinterpret_cast<GradClipRecord*>(static_cast<char*>(k.scratch) + GCLIP_RECORD_OFF);
-    hipLaunchKernelGGL(grad_clip_finalize_kernel, dim3(1), dim3(256), 0, st, f);
-    LAUNCH_CHECK("grad_clip_finalize_kernel");
-    return 0;
+    return launch("grad_clip_finalize_kernel", grad_clip_finalize_kernel, dim3(1), dim3(256), 0, st, f);
 }
 static int adamw_step_clipped(float* params, const float* grads, float* m, float* v, int ngroups, const int64_t* offsets,
                               const int64_t* sizes, const double* lrs, const double* beta1s, double beta2, double eps, double weight_decay,
                               float grad_scale, const ClipArgs& k, hipStream_t st) {
     if (launch_grad_norm(grads, ngroups, offsets, sizes, grad_scale, lrs, beta1s, beta2, k, true, st)) return -1;
     AdamArgs a;
-    // vae_adamw_step's scalars; step_size and inv_sqrt_bc2 come from the record (the step count lives on the device)
-    a.p = params; a.g = grads; a.m = m; a.v = v; a.ngrp = ngroups; a.beta2 = (float)beta2; a.omb2 = (float)(1.0 - beta2); a.eps = (float)eps;
-    a.grad_scale = grad_scale; a.step = 0;
-    long nmax = 0;
-    for (int i = 0; i < ngroups; ++i) {
-        a.grp[i].off = offsets[i]; a.grp[i].n = sizes[i]; nmax = std::max<long>(nmax, sizes[i]);
-        a.grp[i].beta1 = (float)beta1s[i]; a.grp[i].omb1 = (float)(1.0 - beta1s[i]); a.grp[i].decay = (float)(1.0 - lrs[i] * weight_decay);
-        a.grp[i].step_size = 0.f; a.grp[i].inv_sqrt_bc2 = 0.f;
-    }
+    const dim3 grid = adam_args(a, params, grads, m, v, ngroups, offsets, sizes, lrs, beta1s, beta2, eps, weight_decay, grad_scale, 0);
     const GradClipRecord* rec = reinterpret_cast<const GradClipRecord*>(static_cast<const char*>(k.scratch) + GCLIP_RECORD_OFF);
-    hipLaunchKernelGGL(adamw_clipped_kernel, dim3((unsigned)std::min<long>((nmax / 4 + 255) / 256 + 1, 2048), ngroups), dim3(256), 0, st, a, rec);
-    LAUNCH_CHECK("adamw_clipped_kernel");
-    return 0;
+    return launch("adamw_clipped_kernel", adamw_clipped_kernel, grid, dim3(256), 0, st, a, rec);
 }
 
 extern "C" int vae_grad_norm(const float* grads, int ngroups, const int64_t* offsets, const int64_t* sizes, float grad_scale,
                              double* norm_out, void* scratch, vae_stream_t stream) {
     if (!grads) return vae_set_error("vae_grad_norm", "null gradient buffer");
-    if (ngroups < 1 || ngroups > 2) return vae_set_error("vae_grad_norm", "1 or 2 groups");
-    if (!offsets || !sizes) return vae_set_error("vae_grad_norm", "null offsets / sizes");
-    for (int i = 0; i < ngroups; ++i)
-        if (offsets[i] < 0 || sizes[i] < 1) return vae_set_error("vae_grad_norm", "empty or negative range");
+    if (check_groups("vae_grad_norm", ngroups, offsets, sizes)) return -1;
     if (!norm_out || !scratch) return vae_set_error("vae_grad_norm", "null device pointer (norm_out, scratch)");
     if ((uintptr_t)scratch % 16) return vae_set_error("vae_grad_norm", "scratch must be 16-byte aligned");
     ClipArgs k = {0.0, 0, nullptr, norm_out, nullptr, scratch};
@@ -1111,6 +861,12 @@ extern "C" int vae_profile(vae_ctx* c, int enable) {
     c->prof_recs.clear(); c->prof = enable;
     return 0;
 }
+// the end of every profile writer: the text and its NUL into (buf, cap), or a refusal
+static int copy_text(const char* what, const std::string& out, char* buf, int64_t cap) {
+    if ((int64_t)out.size() + 1 > cap) return vae_set_error(what, "buffer too small");
+    memcpy(buf, out.c_str(), out.size() + 1);
+    return 0;
+}
 // JSON: [{"name":..,"calls":n,"ms":total,"bytes":total algorithmic bytes,"flops":total}, ...]
 extern "C" int vae_profile_report(vae_ctx* c, char* buf, int64_t cap) {
     if (!c) return vae_set_error("vae_profile_report", "null ctx");
@@ -1133,9 +889,7 @@ extern "C" int vae_profile_report(vae_ctx* c, char* buf, int64_t cap) {
         out += line;
     }
     out += "]";
-    if ((int64_t)out.size() + 1 > cap) return vae_set_error("vae_profile_report", "buffer too small");
-    memcpy(buf, out.c_str(), out.size() + 1);
-    return 0;
+    return copy_text("vae_profile_report", out, buf, cap);
 }
 
 // JSON array of the profiled launch labels in launch order (for matching rocprofv3 dispatches to labels)
@@ -1145,9 +899,7 @@ extern "C" int vae_profile_sequence(vae_ctx* c, char* buf, int64_t cap) {
     for (size_t i = 0; i < c->prof_recs.size(); ++i)
         for (int k = 0; k < c->prof_recs[i].launches; ++k) out += std::string(out.size() > 1 ? "," : "") + "\"" + c->prof_recs[i].name + "\"";
     out += "]";
-    if ((int64_t)out.size() + 1 > cap) return vae_set_error("vae_profile_sequence", "buffer too small");
-    memcpy(buf, out.c_str(), out.size() + 1);
-    return 0;
+    return copy_text("vae_profile_sequence", out, buf, cap);
 }
 
 // JSON: [[name, start_ms, end_ms, algorithmic_bytes], ...] relative to the first recorded launch (shows the overlap of the streams)
@@ -1163,9 +915,7 @@ extern "C" int vae_profile_timeline(vae_ctx* c, char* buf, int64_t cap) {
         out += std::string(i ? ",[\"" : "[\"") + c->prof_recs[i].name + tmp;
     }
     out += "]";
-    if ((int64_t)out.size() + 1 > cap) return vae_set_error("vae_profile_timeline", "buffer too small");
-    memcpy(buf, out.c_str(), out.size() + 1);
-    return 0;
+    return copy_text("vae_profile_timeline", out, buf, cap);
 }
 
 extern "C" int vae_pre_latents(vae_ctx* c, float* out, vae_stream_t stream) {
@@ -1207,75 +957,4 @@ extern "C" int vae_debug_tensor(vae_ctx* c, int which, float* out, int64_t capac
     const long n = (long)c->fwd.B * C * HW;
     if (n > capacity) return vae_set_error("vae_debug_tensor", "output too small");
     return VAE_DISPATCH(c->dtype, debug_tensor_impl, (c, src, out, n, C, HW, (hipStream_t)stream));
-}
-
-// Self-test of ds_read_b64_tr_b16: a 16x32 tile of 16-bit words M[k][c] = k*32 + c staged as
-// [k][c]; the k-major fragment of lane (r,h) must come back as M[8h+j][r].
-__global__ void selftest_tr16_kernel(int* bad) {
-    __shared__ __attribute__((aligned(16))) short tile[16 * 32];
-    const int lane = threadIdx.x;
-    for (int i = lane; i < 16 * 32; i += 64) tile[i] = (short)i;
-    __syncthreads();
-    const int g4 = lane >> 4, li = lane & 15, q = li >> 2, p = li & 3, r = lane & 31, h = lane >> 5;
-    int nbad = 0;
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        const int k = 8 * (g4 >> 1) + 4 * half + q;
-        const char* ad = reinterpret_cast<const char*>(tile) + k * 64 + (16 * (g4 & 1) + 4 * p) * 2;
-        s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))ad);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if ((int)v[e] != (8 * h + 4 * half + e) * 32 + r) ++nbad;
-    }
-    if (nbad) atomicAdd(bad, nbad);
-}
-// Kernel-shaped variant: rows at an arbitrary pitch/base, row gather at stride (the wgrad G operand).
-__global__ void selftest_tr16b_kernel(int* bad, int* info, int pitch, int base, int rowstride) {
-    extern __shared__ __attribute__((aligned(16))) char sm[];
-    const int lane = threadIdx.x;
-    short* t = reinterpret_cast<short*>(sm);
-    for (int i = lane; i < 8192; i += 64) t[i] = (short)(i * 7 + 3);
-    __syncthreads();
-    const int g4 = lane >> 4, li = lane & 15, q = li >> 2, p = li & 3, r = lane & 31, h = lane >> 5;
-    int nbad = 0;
-    for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-            const int k = ks * 16 + 8 * (g4 >> 1) + 4 * half + q;
-            const char* ad = sm + base + (k * rowstride) * pitch + (16 * (g4 & 1) + 4 * p) * 2;
-            s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((LDS_PTR(s16x4))ad);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int kk = ks * 16 + 8 * h + 4 * half + e;
-                const short want = *reinterpret_cast<const short*>(sm + base + (kk * rowstride) * pitch + r * 2);
-                if (v[e] != want) { if (nbad == 0 && lane < 64) { info[lane * 4] = ks * 100 + half * 10 + e; info[lane * 4 + 1] = v[e]; info[lane * 4 + 2] = want; } ++nbad; }
-            }
-        }
-    }
-    if (nbad) atomicAdd(bad, nbad);
-}
-extern "C" int vae_selftest_tr16(vae_stream_t stream) {
-    int* d = nullptr; int h[1 + 256];
-    HIP_CHECK_RET(hipMalloc(&d, sizeof(h)));
-    const int cfgs[5][3] = {{64, 0, 1}, {144, 1536, 1}, {80, 768, 1}, {144, 1536, 2}, {80, 768, 3}};
-    std::string msg;
-    HIP_CHECK_RET(hipMemsetAsync(d, 0, sizeof(h), (hipStream_t)stream));
-    hipLaunchKernelGGL(selftest_tr16_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, d);
-    HIP_CHECK_RET(hipMemcpyAsync(h, d, 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIP_CHECK_RET(hipStreamSynchronize((hipStream_t)stream));
-    if (h[0]) msg += "basic:" + std::to_string(h[0]) + " ";
-    for (int c = 0; c < 5; ++c) {
-        HIP_CHECK_RET(hipMemsetAsync(d, 0, sizeof(h), (hipStream_t)stream));
-        hipLaunchKernelGGL(selftest_tr16b_kernel, dim3(1), dim3(64), 16384, (hipStream_t)stream, d, d + 1, cfgs[c][0], cfgs[c][1], cfgs[c][2]);
-        HIP_CHECK_RET(hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, (hipStream_t)stream));
-        HIP_CHECK_RET(hipStreamSynchronize((hipStream_t)stream));
-        if (h[0]) {
-            msg += "cfg" + std::to_string(c) + ":" + std::to_string(h[0]) + "[";
-            for (int l = 0; l < 64; l += 9) msg += "L" + std::to_string(l) + ":" + std::to_string(h[1 + l * 4]) + "," + std::to_string(h[2 + l * 4]) + "," + std::to_string(h[3 + l * 4]) + " ";
-            msg += "] ";
-        }
-    }
-    (void)hipFree(d);
-    if (!msg.empty()) return vae_set_error("ds_read_b64_tr_b16 self-test", msg.c_str());
-    return 0;
 }

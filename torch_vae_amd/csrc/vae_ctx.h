@@ -1,5 +1,6 @@
-// Host-side context of the VAE step: shared by the C-ABI translation unit (vae_api.hip) and the per-storage-type
-// translation units (impl_bf16.hip / impl_f16.hip / impl_f32.hip) that instantiate the templated launch code.
+// Host-side context of the VAE step: shared by the C-ABI translation units (vae_api.hip; vae_util.hip takes the launch helpers
+// and nothing of the context) and the per-storage-type translation units (impl_bf16.hip / impl_f16.hip / impl_f32.hip) that
+// instantiate the templated launch code.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -8,6 +9,7 @@
 #include <string>
 #include <vector>
 #include <algorithm>
+#include <type_traits>
 
 #include "../../include/vae_step.h"
 
@@ -20,6 +22,43 @@ int vae_set_error(const char* what, const char* why);   // vae_api.hip; message 
         hipError_t _e = hipGetLastError();                                        \
         if (_e != hipSuccess) return vae_set_error(name, hipGetErrorString(_e)); \
     } while (0)
+
+// Every kernel the host code launches starts here, so that the dynamic-LDS limit is raised before every launch that needs it (above
+// 48 KiB; nothing fits above 160 KiB) and the launch error is read after every launch (reported under `name`).  Nothing else.
+template <typename K, typename... Args>
+static int launch(const char* name, K kernel, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const Args&... args) {
+    if (lds_bytes > 160 * 1024) return vae_set_error("lds", "tile needs more than 160 KiB LDS");
+    if (lds_bytes > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (e != hipSuccess) return vae_set_error("hipFuncSetAttribute", hipGetErrorString(e));
+    }
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, st, args...);
+    LAUNCH_CHECK(name);
+    return 0;
+}
+
+// Run-time value -> template argument: returns f(std::integral_constant<int, V>{}) for the V of Vs... that equals v, an error
+// under `what` (the launch) when none does.  f is instantiated for every V listed and for no other, so a call site names exactly
+// the kernel variants that exist.
+template <int... Vs, typename F>
+static int pick_const(const char* what, int v, F&& f) {
+    int rc = 0;
+    const bool found = ((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
+    return found ? rc : vae_set_error(what, "no kernel variant for this value");
+}
+template <typename F> static int pick_bool(bool v, F&& f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
+
+// Work space of `bytes` from the stream-ordered allocator for what body(char* base) enqueues on `st`; freed on the stream behind
+// it whatever body returned.  body's error wins over a failed free; a failed allocation returns before body runs.
+template <typename F> static int with_stream_scratch(size_t bytes, hipStream_t st, F&& body) {
+    void* ws = nullptr;
+    HIP_CHECK_RET(hipMallocAsync(&ws, bytes, st));
+    const int rc = body(static_cast<char*>(ws));
+    const hipError_t fe = hipFreeAsync(ws, st);
+    if (rc) return rc;
+    if (fe != hipSuccess) return vae_set_error("hipFreeAsync", hipGetErrorString(fe));
+    return 0;
+}
 
 static const int kBnC[8] = {32, 64, 128, 256, 128, 64, 32, 32};
 static const char* const kLayerTag[8] = {"encoder.0", "encoder.1", "encoder.2", "encoder.3", "decoder.0", "decoder.1", "decoder.2", "final_layer.0"};   // profiling / debug tag of BN layer i

@@ -1,7 +1,6 @@
 // Launch sequencing of the VAE step, templated on the storage type T (bf16 / f16 / float).  Included by one
 // translation unit per storage type, which instantiates the entry points declared at the end of vae_ctx.h.
 #pragma once
-#include <type_traits>
 #include "vae_ctx.h"
 #include "conv_mfma.cuh"
 #include "conv_pipe.cuh"
@@ -15,31 +14,6 @@
 #include "dnfirst_stream.cuh"
 #include "grad_paths.cuh"
 
-// ---------------------------------------------------------------------------
-// Every kernel of this file starts here, so that the dynamic-LDS limit is raised before every launch that needs it (above
-// 48 KiB; nothing fits above 160 KiB) and the launch error is read after every launch (reported under `name`).  Nothing else.
-template <typename K, typename... Args>
-static int launch(const char* name, K kernel, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t st, const Args&... args) {
-    if (lds_bytes > 160 * 1024) return vae_set_error("lds", "tile needs more than 160 KiB LDS");
-    if (lds_bytes > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return vae_set_error("hipFuncSetAttribute", hipGetErrorString(e));
-    }
-    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, st, args...);
-    LAUNCH_CHECK(name);
-    return 0;
-}
-
-// Run-time value -> template argument: returns f(std::integral_constant<int, V>{}) for the V of Vs... that equals v, an error
-// under `what` (the launch) when none does.  f is instantiated for every V listed and for no other, so a call site names exactly
-// the kernel variants that exist.
-template <int... Vs, typename F>
-static int pick_const(const char* what, int v, F&& f) {
-    int rc = 0;
-    const bool found = ((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
-    return found ? rc : vae_set_error(what, "no kernel variant for this value");
-}
-template <typename F> static int pick_bool(bool v, F&& f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
 // the reconstruction term the held forward ran with
 template <typename F> static int pick_recon(vae_ctx* c, F&& f) {
     return c->fwd.recon == VAE_RECON_MSE ? f(std::integral_constant<int, VAE_RECON_MSE>{}) : f(std::integral_constant<int, VAE_RECON_BCE>{});
