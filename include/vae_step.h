@@ -129,9 +129,26 @@ int vae_elbo_generic(const float* xhat, const float* target, const float* mu, co
  * out3 keeps its meaning: reconstruction_loss is the chosen term, loss = reconstruction_loss + kld_weight * KL. */
 #define VAE_RECON_BCE 0
 #define VAE_RECON_MSE 1
+/* WBCE: BCE with a positive-class weight w = pos_weight against the sparsity of pianorolls (a few percent of the cells are notes,
+ * so "all silent" is a very good solution of the plain mean).  Per cell, with the target t in [0, 1] and W = 1 + (w - 1) t:
+ *   reconstruction_loss = mean over B*H*W of W * bce(xhat, t)   = F.binary_cross_entropy(xhat, x, weight = 1 + (w - 1) x)
+ *   dL/dlogit           = the BCE dlogit * W
+ * The mean divides by N = B*H*W, not by the weight sum, as torch does; the logs keep their -100 clamp; W multiplies after the
+ * unweighted term and gradient, in ATen's order, so w = 1 gives the bits of VAE_RECON_BCE.  For 0/1 rolls this is exactly
+ * BCEWithLogitsLoss(pos_weight = w).  For velocity rolls the weight grows with how much of a note the cell is and the per-cell
+ * optimum stays xhat = t; multiplying only the positive log term would move the optimum, which is why the weight is on the cell.
+ * w is a finite number in (0, 1024].  kld_loss, the KL objectives and loss = reconstruction_loss + kld_weight * T are untouched.
+ * f16 storage: |dlogit| is bounded by w/N instead of 1/N, so for w > 1 the power-of-two gradient scale of the forward is lowered
+ * by 2^ceil(log2 w) (not below 1): the scaled dlogit keeps the bound it has for BCE. */
+#define VAE_RECON_WBCE 2
 /* reconstruction term of the ELBO for the following forwards of this context (sticky; default BCE).  A forward records
  * the setting: its loss, deferred output conv (train = 2) and backward use the recorded term even if it changes after. */
 int vae_set_recon_loss(vae_ctx* ctx, int kind);
+/* vae_set_recon_loss for every kind, with the kind's parameter: pos_weight for VAE_RECON_WBCE, 0 for VAE_RECON_BCE / VAE_RECON_MSE.
+ * Sticky and recorded by a forward like the kind (its deferred output conv, loss and backward use the recorded weight).  Enqueues
+ * nothing: it may be called every step.  Returns -1 for an unknown kind, a pos_weight that is NaN, infinite, <= 0 or > 1024, or a
+ * non-zero param with BCE / MSE.  (vae_set_recon_loss itself keeps refusing every kind but BCE / MSE.) */
+int vae_set_recon_loss_ex(vae_ctx* ctx, int kind, double param);
 /* vae_elbo_generic with the reconstruction term chosen per call (recon: VAE_RECON_*); for MSE g_xhat = (xhat - t) * 2/n. */
 int vae_elbo_generic_ex(const float* xhat, const float* target, const float* mu, const float* log_var, int64_t n,
                         int batch, int latent_dim, float kld_weight, int recon, float* out3, float* g_xhat,
@@ -170,6 +187,12 @@ int vae_set_kl_objective(vae_ctx* ctx, int kind, double param);
 int vae_elbo_generic_kl(const float* xhat, const float* target, const float* mu, const float* log_var, int64_t n,
                         int batch, int latent_dim, float kld_weight, int recon, int kl_kind, double kl_param, float* out3,
                         float* g_xhat, float* g_mu, float* g_log_var, vae_stream_t stream);
+/* vae_elbo_generic_kl with the reconstruction term's parameter (recon_param: as vae_set_recon_loss_ex's param), the only generic
+ * entry point that takes VAE_RECON_WBCE: g_xhat = W * (xhat - t) / max(xhat (1 - xhat), 1e-12) / n.  A bad kind or weight returns
+ * -1 before anything is enqueued. */
+int vae_elbo_generic_w(const float* xhat, const float* target, const float* mu, const float* log_var, int64_t n,
+                       int batch, int latent_dim, float kld_weight, int recon, double recon_param, int kl_kind, double kl_param,
+                       float* out3, float* g_xhat, float* g_mu, float* g_log_var, vae_stream_t stream);
 /* kl_d [latent_dim] f64 of the last forward (vae_forward, the training steps, vae_encode), device memory, no host
  * synchronisation: the forward's own reduction when it ran with an objective other than plain, else reduced on demand. */
 int vae_kl_per_dim(vae_ctx* ctx, double* out, vae_stream_t stream);
@@ -193,7 +216,9 @@ int vae_last_total_correlation(vae_ctx* ctx, double* out, vae_stream_t stream);
  *   elbo[b]           = mean_k log p(x_b|z_kb) - KL(q(z|x_b) || N(0, I))
  * log p(x|z) follows the context's reconstruction term (vae_set_recon_loss): BCE - Bernoulli, sum over pixels of
  * t log xhat + (1-t) log(1-xhat) with the logs clamped at -100 (normalised only for 0/1 targets); MSE - Gaussian of variance 1/2,
- * -sum (xhat - t)^2 - (H*W/2) log(pi).  BatchNorm uses (and never writes) the running statistics in bn_running.  Nothing is
+ * -sum (xhat - t)^2 - (H*W/2) log(pi).  VAE_RECON_WBCE counts as BCE here: a weighted BCE is not a likelihood, so log p(x|z), the
+ * IWAE bound and the per-sample ELBO stay the unweighted Bernoulli whatever pos_weight is.  BatchNorm uses (and never writes) the
+ * running statistics in bn_running.  Nothing is
  * left to differentiate: vae_loss / vae_backward after this call fail until the next forward. */
 int vae_log_likelihood(vae_ctx* ctx, const float* x, int batch, const float* params, const float* bn_running,
                        int num_samples, int chunk, const float* eps, uint64_t seed,

@@ -19,6 +19,8 @@ DTYPE_BF16 = 1
 DTYPE_F16 = 2
 RECON_BCE = 0
 RECON_MSE = 1
+RECON_WBCE = 2      # include/vae_step.h: BCE with a positive-class weight (vae_set_recon_loss_ex)
+POS_WEIGHT_MAX = 1024.0
 KL_PLAIN = 0        # include/vae_step.h: VAE_KL_*
 KL_FREE_BITS = 1
 KL_CAPACITY = 2
@@ -78,8 +80,10 @@ def lib():
     _sig(L.vae_elbo_generic, i32, [p, p, p, p, i64, i32, i32, f32, p, p, p, p, p])
     _sig(L.vae_elbo_generic_ex, i32, [p, p, p, p, i64, i32, i32, f32, i32, p, p, p, p, p])
     _sig(L.vae_set_recon_loss, i32, [p, i32])
+    _sig(L.vae_set_recon_loss_ex, i32, [p, i32, f64])
     _sig(L.vae_set_kl_objective, i32, [p, i32, f64])
     _sig(L.vae_elbo_generic_kl, i32, [p, p, p, p, i64, i32, i32, f32, i32, i32, f64, p, p, p, p, p])
+    _sig(L.vae_elbo_generic_w, i32, [p, p, p, p, i64, i32, i32, f32, i32, f64, i32, f64, p, p, p, p, p])
     _sig(L.vae_kl_per_dim, i32, [p, p, p])
     _sig(L.vae_total_correlation, i32, [p, p, p, i32, i32, p, p, p, p])
     _sig(L.vae_last_total_correlation, i32, [p, p, p])
@@ -124,7 +128,7 @@ def lib():
 EXPORTS = [
     "vae_last_error", "vae_abi_version", "vae_param_layout", "vae_bn_layout", "vae_create", "vae_destroy",
     "vae_workspace_bytes", "vae_forward", "vae_decode", "vae_pre_latents", "vae_last_eps", "vae_loss", "vae_loss_deferred", "vae_elbo_generic",
-    "vae_set_recon_loss", "vae_elbo_generic_ex", "vae_set_kl_objective", "vae_elbo_generic_kl", "vae_kl_per_dim", "vae_total_correlation", "vae_last_total_correlation", "vae_log_likelihood", "vae_latent_stats",
+    "vae_set_recon_loss", "vae_set_recon_loss_ex", "vae_elbo_generic_ex", "vae_set_kl_objective", "vae_elbo_generic_kl", "vae_elbo_generic_w", "vae_kl_per_dim", "vae_total_correlation", "vae_last_total_correlation", "vae_log_likelihood", "vae_latent_stats",
     "vae_recon_metrics",
     "vae_backward", "vae_backward_part", "vae_encode", "vae_backward_ex", "vae_comm_stream", "vae_comm_unique_id", "vae_comm_init", "vae_comm_world",
     "vae_comm_destroy", "vae_allreduce_grads", "vae_broadcast_state", "vae_adamw_step", "vae_train_step", "vae_train_step_fused",

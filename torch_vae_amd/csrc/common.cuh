@@ -169,22 +169,34 @@ __device__ __forceinline__ double wave_sum(double v) {
 // vae_set_recon_loss).  N = B*H*W, inv_n = 1/N; dlogit is ATen's loss backward followed by sigmoid_backward, in ATen's order:
 //   BCE: -(t*max(log xhat,-100) + (1-t)*max(log(1-xhat),-100))   dlogit = (xhat-t)/max(xhat(1-xhat),1e-12) * xhat(1-xhat) / N
 //   MSE: (xhat-t)^2                                                dlogit = ((xhat-t) * 2/N) * (1-xhat) * xhat
+//   WBCE: BCE term * W                                             dlogit = BCE dlogit * W,   W = 1 + (w - 1) t
 // (2*inv_n is 2/N rounded once: a power-of-two scale is exact.)  The kernels sum the per-pixel term; the mean is a0 * inv_n.
-template <int RECON> __device__ __forceinline__ float recon_term(float xh, float tg) {
+// WBCE is F.binary_cross_entropy(xhat, t, weight = W): w = pos_weight, a run-time float in the kernel's argument struct (recon_w;
+// vae_set_recon_loss_ex).  The weight is on the CELL, growing with how much of a note the target is, not on the positive log term
+// alone: for a velocity target 0 < t < 1 the per-cell optimum stays xhat = t (weighting only t log xhat would move it), and for 0/1
+// targets the two forms are the same BCEWithLogitsLoss(pos_weight = w).  W multiplies last, after the unweighted term and gradient
+// (ATen's order), so w = 1 gives the bits of BCE: W is then exactly 1.  BCE and MSE never read w: their instantiations are the
+// code they were without it.
+__device__ __forceinline__ float recon_cell_weight(float tg, float w) { return 1.f + (w - 1.f) * tg; }
+template <int RECON> __device__ __forceinline__ float recon_term(float xh, float tg, float w = 1.f) {
     if constexpr (RECON == VAE_RECON_MSE) {
         const float d = xh - tg;
         return d * d;
     } else {
         const float l1 = fmaxf(logf(xh), -100.f), l0 = fmaxf(logf(1.f - xh), -100.f);
-        return -(tg * l1 + (1.f - tg) * l0);
+        const float term = -(tg * l1 + (1.f - tg) * l0);
+        if constexpr (RECON == VAE_RECON_WBCE) return term * recon_cell_weight(tg, w);
+        else return term;
     }
 }
-template <int RECON> __device__ __forceinline__ float recon_dlogit(float xh, float tg, float inv_n) {
+template <int RECON> __device__ __forceinline__ float recon_dlogit(float xh, float tg, float inv_n, float w = 1.f) {
     if constexpr (RECON == VAE_RECON_MSE) {
         return (xh - tg) * (2.f * inv_n) * (1.f - xh) * xh;
     } else {
         const float om = xh * (1.f - xh);
-        return (xh - tg) / fmaxf(om, 1e-12f) * om * inv_n;
+        const float dl = (xh - tg) / fmaxf(om, 1e-12f) * om * inv_n;
+        if constexpr (RECON == VAE_RECON_WBCE) return dl * recon_cell_weight(tg, w);
+        else return dl;
     }
 }
 

@@ -707,6 +707,7 @@ template <typename T> struct ConvOutFwdMfmaArgs {
     int B, H, W, n_tiles; float inv_n, slope;
     BnFuse fuse;
     int rev;
+    float recon_w;                              // VAE_RECON_WBCE: pos_weight (in the struct's padding: no other member moves)
     double* part; int tB;                       // per-sample mode only
 };
 
@@ -814,14 +815,14 @@ __global__ __launch_bounds__(256, 2) void convout_fwd_mfma_kernel(ConvOutFwdMfma
             const float xh = 1.f / (1.f + expf(-logit));
             if constexpr (PS) {
                 // (wred is next written after two more barriers, which thread 0 reaches only after this read)
-                const float ts = wave_sum(recon_term<RECON>(xh, tg));
+                const float ts = wave_sum(recon_term<RECON>(xh, tg, a.recon_w));
                 if (lane == 0) wred[wave] = ts;
                 __syncthreads();
                 if (tid == 0) a.part[(b * tiles_y + y0 / TH) * tiles_x + x0 / TW] = (double)wred[0] + (double)wred[1] + (double)wred[2] + (double)wred[3];
             } else {
-                bsum += recon_term<RECON>(xh, tg);
+                bsum += recon_term<RECON>(xh, tg, a.recon_w);
                 a.xhat[gi] = xh;
-                a.dlogit[gi] = recon_dlogit<RECON>(xh, tg, a.inv_n);
+                a.dlogit[gi] = recon_dlogit<RECON>(xh, tg, a.inv_n, a.recon_w);
             }
         }
     }
@@ -1008,6 +1009,7 @@ template <typename T> struct ConvOutStepArgs {
     float* xhat; double* accum;                 // accum[rep*8 + 0] += reconstruction-term sum, [rep*8 + 2] += sum of dlogit (bias gradient)
     T* dz; float* slab; double* stat;           // stat: sum dz | sum dz*xhat7 of final_layer's BatchNorm (replicated)
     int B, H, W, n_tiles; float inv_n, slope, gmul;
+    float recon_w;                              // VAE_RECON_WBCE: pos_weight (in the struct's padding: no other member moves)
     BnFuse fuse;                                // final_layer BatchNorm finalised in the prologue (forward mode)
     int rev;
     int ablate;                                 // timing diagnostics only (results wrong): 1 forward tap MFMAs, 2 logits, 4 gradient MFMAs, 8 epilogue, 16 dz store
@@ -1136,11 +1138,11 @@ __global__ __launch_bounds__(256, 2) void convout_step_mfma_kernel(ConvOutStepAr
                 for (int t = 0; t < 9; ++t) logit += part[((ry + t / 3) * PW + rx + t % 3) * 9 + t];
                 const float tg = u ? tg1 : tg0;
                 const float xh = 1.f / (1.f + expf(-logit));
-                const float dlv = recon_dlogit<RECON>(xh, tg, a.inv_n);
+                const float dlv = recon_dlogit<RECON>(xh, tg, a.inv_n, a.recon_w);
                 const float dl = (u ? tk1 : tk0) ? dlv * gs : 0.f;
                 dl_s[i] = dl;
                 if (ry >= 1 && ry <= TH && rx >= 1 && rx <= TW) {   // the tile itself
-                    bsum += recon_term<RECON>(xh, tg);
+                    bsum += recon_term<RECON>(xh, tg, a.recon_w);
                     a.xhat[((size_t)b * a.H + y0 + ry - 1) * a.W + x0 + rx - 1] = xh;
                     sdl += dl;
                 }

@@ -40,6 +40,7 @@ template <typename T> struct ConvOutStreamArgs {
     int B, H, RB, nb, n_units; float inv_n, slope, gmul;   // RB rows per band, nb bands per image, n_units = B * nb
     BnFuse fuse;
     long long* dbg;
+    float recon_w;                              // VAE_RECON_WBCE: pos_weight (last: no other member moves)
 };
 
 namespace cos {
@@ -288,14 +289,14 @@ __global__ __launch_bounds__(1024) void convout_stream_kernel(ConvOutStreamArgs<
 #pragma unroll
                     for (int t = 0; t < 9; ++t) logit += part[(((p4 + lrow + t / 3) & 3) * 9 + t) * PPW + 4 + lx + t % 3 - 1];
                     const float xh = 1.f / (1.f + expf(-logit));
-                    const float dlv = recon_dlogit<RECON>(xh, tg, a.inv_n);
+                    const float dlv = recon_dlogit<RECON>(xh, tg, a.inv_n, a.recon_w);
                     const float dl = ok ? dlv * gs : 0.f;
                     const T dlt = (T)dl;
                     T* drow = dlc + ((p4 + 1 + lrow) & 3) * 3 * DLW + lx + 8;
                     drow[-1] = dlt; drow[DLW] = dlt; drow[2 * DLW + 1] = dlt;
                     drow[12 * DLW - 1] = dlt; drow[13 * DLW] = dlt; drow[14 * DLW + 1] = dlt;      // the same row at slot + 4
                     if (ok && R >= r0 && R < r1) {        // the band's own rows
-                        bsum += recon_term<RECON>(xh, tg);
+                        bsum += recon_term<RECON>(xh, tg, a.recon_w);
                         a.xhat[((size_t)(b * H + R)) * RW + lx] = xh;
                         sdl += dl;
                     }

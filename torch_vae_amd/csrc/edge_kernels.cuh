@@ -198,6 +198,7 @@ struct ConvOutArgs {
     float* xhat; float* dlogit;             // [B,H,W]
     double* accum;                          // [0] reconstruction-term sum
     int B, H, W; float inv_n; float slope;
+    float recon_w;                          // VAE_RECON_WBCE: pos_weight (in the struct's padding: no other member moves)
     double* part; int tB;                   // per-sample mode only
 };
 
@@ -246,10 +247,10 @@ __global__ __launch_bounds__(256) void convout_fwd_kernel(ConvOutArgs a) {
         const size_t gi = ((size_t)b * a.H + y0 + oy) * a.W + x0 + ox;
         const float tg = a.target[((size_t)tb * a.H + y0 + oy) * a.W + x0 + ox];
         const float xh = 1.f / (1.f + expf(-logit));
-        bsum += recon_term<RECON>(xh, tg);
+        bsum += recon_term<RECON>(xh, tg, a.recon_w);
         if constexpr (!PS) {
             a.xhat[gi] = xh;
-            a.dlogit[gi] = recon_dlogit<RECON>(xh, tg, a.inv_n);
+            a.dlogit[gi] = recon_dlogit<RECON>(xh, tg, a.inv_n, a.recon_w);
         }
     }
     bsum = wave_sum(bsum);
@@ -285,6 +286,23 @@ static __global__ void bce_kernel(const float* __restrict__ xh_, const float* __
         const float xh = xh_[i], tg = tg_[i];
         bsum += -(tg * fmaxf(logf(xh), -100.f) + (1.f - tg) * fmaxf(logf(1.f - xh), -100.f));
         if (gx) gx[i] = (xh - tg) / fmaxf(xh * (1.f - xh), 1e-12f) * inv_n;
+    }
+    bsum = wave_sum(bsum);
+    if ((threadIdx.x & 63) == 0) wred[threadIdx.x >> 6] = bsum;
+    __syncthreads();
+    if (threadIdx.x == 0) unsafeAtomicAdd(&accum[0], (double)(wred[0] + wred[1] + wred[2] + wred[3]));
+}
+
+// generic F.binary_cross_entropy(mean, weight = 1 + (w - 1) t) forward + grad w.r.t. the prediction: bce_kernel's term and gradient
+// times the cell weight (common.cuh: recon_cell_weight; the clamped logs and the clamped denominator are weighted like the rest)
+static __global__ void wbce_kernel(const float* __restrict__ xh_, const float* __restrict__ tg_, float* __restrict__ gx,
+                            double* __restrict__ accum, long n, float inv_n, float w) {
+    __shared__ float wred[4];
+    float bsum = 0.f;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const float xh = xh_[i], tg = tg_[i], cw = recon_cell_weight(tg, w);
+        bsum += -(tg * fmaxf(logf(xh), -100.f) + (1.f - tg) * fmaxf(logf(1.f - xh), -100.f)) * cw;
+        if (gx) gx[i] = (xh - tg) / fmaxf(xh * (1.f - xh), 1e-12f) * inv_n * cw;
     }
     bsum = wave_sum(bsum);
     if ((threadIdx.x & 63) == 0) wred[threadIdx.x >> 6] = bsum;

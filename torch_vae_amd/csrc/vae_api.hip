@@ -391,7 +391,21 @@ extern "C" int vae_log_likelihood(vae_ctx* c, const float* x, int B, const float
 extern "C" int vae_set_recon_loss(vae_ctx* c, int kind) {
     if (!c) return vae_set_error("vae_set_recon_loss", "null ctx");
     if (kind != VAE_RECON_BCE && kind != VAE_RECON_MSE) return vae_set_error("vae_set_recon_loss", "kind must be VAE_RECON_BCE or VAE_RECON_MSE");
-    c->recon = kind;
+    c->recon = kind; c->recon_param = 0.0;
+    return 0;
+}
+// kind and parameter of a reconstruction term (vae_set_recon_loss_ex, vae_elbo_generic_w): pos_weight of WBCE a finite number in (0, 1024]
+static int check_recon(const char* what, int kind, double param) {
+    if (kind != VAE_RECON_BCE && kind != VAE_RECON_MSE && kind != VAE_RECON_WBCE) return vae_set_error(what, "recon must be VAE_RECON_BCE, VAE_RECON_MSE or VAE_RECON_WBCE");
+    if (kind == VAE_RECON_WBCE) {
+        if (!(param > 0.0) || !(param <= 1024.0)) return vae_set_error(what, "pos_weight must be a finite number in (0, 1024]");   // (a NaN fails both comparisons)
+    } else if (param != 0.0) return vae_set_error(what, "the parameter must be 0 for VAE_RECON_BCE / VAE_RECON_MSE");
+    return 0;
+}
+extern "C" int vae_set_recon_loss_ex(vae_ctx* c, int kind, double param) {
+    if (!c) return vae_set_error("vae_set_recon_loss_ex", "null ctx");
+    if (check_recon("vae_set_recon_loss_ex", kind, param)) return -1;
+    c->recon = kind; c->recon_param = kind == VAE_RECON_WBCE ? param : 0.0;
     return 0;
 }
 
@@ -577,8 +591,9 @@ static double* g_generic_ring[kMaxDevices] = {nullptr};
 static unsigned g_generic_next[kMaxDevices] = {0};
 static int elbo_generic(const char* what, const float* xhat, const float* target, const float* mu, const float* lv, int64_t n, int B, int L,
                         float kld_weight, int recon, int kl_kind, double kl_param, float* out3, float* g_xhat, float* g_mu, float* g_lv,
-                        vae_stream_t stream) {
-    if (recon != VAE_RECON_BCE && recon != VAE_RECON_MSE) return vae_set_error(what, "recon must be VAE_RECON_BCE or VAE_RECON_MSE");
+                        vae_stream_t stream, double recon_param = 0.0, bool allow_wbce = false) {
+    if (!allow_wbce && recon != VAE_RECON_BCE && recon != VAE_RECON_MSE) return vae_set_error(what, "recon must be VAE_RECON_BCE or VAE_RECON_MSE");
+    if (check_recon(what, recon, recon_param)) return -1;
     if (check_kl_objective(what, kl_kind, kl_param)) return -1;
     if (kl_kind != VAE_KL_PLAIN && (B < 1 || L < 1 || !mu || !lv)) return vae_set_error(what, "the KL objective needs mu / log_var [batch, latent_dim]");
     hipStream_t st = (hipStream_t)stream;
@@ -590,6 +605,7 @@ static int elbo_generic(const char* what, const float* xhat, const float* target
     HIP_CHECK_RET(hipMemsetAsync(acc, 0, 4 * sizeof(double), st));
     const dim3 grid((unsigned)std::min<long>((n + 255) / 256, 2048));
     const int rc = recon == VAE_RECON_MSE ? launch("mse_kernel", mse_kernel, grid, dim3(256), 0, st, xhat, target, g_xhat, acc, (long)n, (float)(2.0 / (double)n))
+                 : recon == VAE_RECON_WBCE ? launch("wbce_kernel", wbce_kernel, grid, dim3(256), 0, st, xhat, target, g_xhat, acc, (long)n, (float)(1.0 / (double)n), (float)recon_param)
                                            : launch("bce_kernel", bce_kernel, grid, dim3(256), 0, st, xhat, target, g_xhat, acc, (long)n, (float)(1.0 / (double)n));
     if (rc) return -1;
     // the KL term and the scalars; factor / scal null and FL 1: the plain objective
@@ -617,6 +633,12 @@ extern "C" int vae_elbo_generic_kl(const float* xhat, const float* target, const
                                    float kld_weight, int recon, int kl_kind, double kl_param, float* out3, float* g_xhat, float* g_mu,
                                    float* g_lv, vae_stream_t stream) {
     return elbo_generic("vae_elbo_generic_kl", xhat, target, mu, lv, n, B, L, kld_weight, recon, kl_kind, kl_param, out3, g_xhat, g_mu, g_lv, stream);
+}
+extern "C" int vae_elbo_generic_w(const float* xhat, const float* target, const float* mu, const float* lv, int64_t n, int B, int L,
+                                  float kld_weight, int recon, double recon_param, int kl_kind, double kl_param, float* out3, float* g_xhat,
+                                  float* g_mu, float* g_lv, vae_stream_t stream) {
+    return elbo_generic("vae_elbo_generic_w", xhat, target, mu, lv, n, B, L, kld_weight, recon, kl_kind, kl_param, out3, g_xhat, g_mu, g_lv, stream,
+                        recon_param, true);
 }
 extern "C" int vae_elbo_generic(const float* xhat, const float* target, const float* mu, const float* lv, int64_t n, int B, int L,
                                 float kld_weight, float* out3, float* g_xhat, float* g_mu, float* g_lv, vae_stream_t stream) {

@@ -106,9 +106,10 @@ struct FwdRecord {
     enum Kind { NONE, FULL, ENCODE, DECODE };   // FULL: vae_forward and the training steps; vae_backward_ex differentiates whichever it was
     Kind kind = NONE;
     int B = 0, trained = 0;                      // batch (the batch statistics' count); the forward's `train` argument
-    // settings the forward ran with (vae_set_recon_loss / vae_set_kl_objective at that time): its deferred output conv, loss and
+    // settings the forward ran with (vae_set_recon_loss[_ex] / vae_set_kl_objective at that time): its deferred output conv, loss and
     // backward use these, whatever the context's settings are by then.  Kinds without an ELBO record VAE_KL_PLAIN.
-    int recon = VAE_RECON_BCE, kl_kind = VAE_KL_PLAIN; double kl_param = 0.0;
+    // recon_param: pos_weight of VAE_RECON_WBCE (0 for the other terms).
+    int recon = VAE_RECON_BCE, kl_kind = VAE_KL_PLAIN; double kl_param = 0.0; double recon_param = 0.0;
     int kl_pending = 0;                          // kl_shape_kernel / the tc_* kernels of this forward are in flight on side stream KL_SIDE: consumers wait for ev_kl
     int kl_reduced = 0;                          // kl_shape_kernel ran for this forward: kl_d and KL are in kl_ws (behind ev_kl)
     int tc_done = 0;                             // this forward's total correlation and its gradient are in tc_ws (launch_tc; behind ev_kl as well)
@@ -178,8 +179,8 @@ struct vae_ctx {
         knob_convout_grid, knob_convout_bwd_grid, knob_convout_step_grid, knob_convout_bands, knob_wgrad_layer_wgs,
         knob_skip_wgrad, knob_ablate_b, knob_ablate_f;
     WgradKnobs wk;
-    // ---- settings for the forwards that follow (vae_set_recon_loss, vae_set_kl_objective); a forward snapshots them into its record ----
-    int recon = VAE_RECON_BCE, kl_kind = VAE_KL_PLAIN; double kl_param = 0.0;
+    // ---- settings for the forwards that follow (vae_set_recon_loss[_ex], vae_set_kl_objective); a forward snapshots them into its record ----
+    int recon = VAE_RECON_BCE, kl_kind = VAE_KL_PLAIN; double kl_param = 0.0; double recon_param = 0.0;
     // ---- the last forward ----
     FwdRecord fwd;
     // ---- diagnostics: phase stamps (vae_debug_stamps) and per-kernel timing (bench.py roofline: HIP events on the launch stream) ----
@@ -227,9 +228,17 @@ static inline size_t wgrad_slab_floats(const WgradKnobs& k, int B, int Hs, int W
 // f16 storage: the gradient scale of a backward over B images (FwdRecord::gmul / ginv); 1 for the other storage types
 static inline void set_grad_scale(vae_ctx* c, int B) {
     // dL/dlogit is O(1/(B*H*W)), far below the smallest f16 normal; 2^ceil(log2(B*H*W)) / 16 puts the stored dz around 2^-4, mid-range
+    // VAE_RECON_WBCE (the record's recon / recon_param are set before this runs): |dlogit| <= w/N instead of 1/N, since |BCE dlogit|
+    // <= 1/N and the cell weight 1 + (w - 1) t lies between 1 and w.  For w > 1 the exponent is lowered by k = ceil(log2 w), clamped
+    // at 0: w / 2^k <= 1, so |dlogit * gmul| <= 2^e0 / N with e0 the BCE exponent - the bound every stored product downstream was
+    // sized for; nothing can overflow that could not with BCE.  The price is range at the bottom: the non-note cells (W = 1) sit k
+    // binades lower, 2^-(4+k) typical; at the largest weight (k = 10) that is still 2^-14, the smallest f16 normal, and the f16
+    // layer-local gate holds at w = 8 and 32 (tests/test_pos_weight_gpu.py).  w <= 1 only shrinks the gradient: unchanged.
     c->fwd.gmul = 1.f; c->fwd.ginv = 1.f;
     if (c->dtype == VAE_DTYPE_F16) {
-        const int e = std::max(0, ilog2(B) + 2 * ilog2(c->H) - 4);
+        int e = std::max(0, ilog2(B) + 2 * ilog2(c->H) - 4);
+        // (only a forward that an ELBO follows: vae_encode / vae_decode have no reconstruction gradient of the library's)
+        if (c->fwd.kind == FwdRecord::FULL && c->fwd.recon == VAE_RECON_WBCE && c->fwd.recon_param > 1.0) e = std::max(0, e - (int)ceil(log2(c->fwd.recon_param)));
         c->fwd.gmul = ldexpf(1.f, e); c->fwd.ginv = ldexpf(1.f, -e);
     }
 }
@@ -250,7 +259,7 @@ static inline int begin_forward(vae_ctx* c, FwdRecord::Kind kind, int B, int tra
     drop_forward(c);
     HIP_CHECK_RET(hipMemsetAsync(c->dstats, 0, c->n_dstats * sizeof(double), st));
     FwdRecord& f = c->fwd;
-    f.kind = kind; f.B = B; f.trained = train; f.bwd_dirty = 0; f.recon = c->recon;
+    f.kind = kind; f.B = B; f.trained = train; f.bwd_dirty = 0; f.recon = c->recon; f.recon_param = c->recon_param;
     const bool elbo = kind == FwdRecord::FULL;   // (no ELBO follows an encoder-only or decoder-only pass)
     f.kl_kind = elbo ? c->kl_kind : VAE_KL_PLAIN; f.kl_param = elbo ? c->kl_param : 0.0;
     f.x = nullptr; f.xhat = f.mu = f.lv = f.z = nullptr;

@@ -14,9 +14,14 @@
 #include "dnfirst_stream.cuh"
 #include "grad_paths.cuh"
 
-// the reconstruction term the held forward ran with
+// the reconstruction term the held forward ran with (its weight, where it has one, is FwdRecord::recon_param -> the kernel's recon_w)
 template <typename F> static int pick_recon(vae_ctx* c, F&& f) {
-    return c->fwd.recon == VAE_RECON_MSE ? f(std::integral_constant<int, VAE_RECON_MSE>{}) : f(std::integral_constant<int, VAE_RECON_BCE>{});
+    return pick_const<VAE_RECON_BCE, VAE_RECON_MSE, VAE_RECON_WBCE>("reconstruction term", c->fwd.recon, f);
+}
+// the per-sample launches of vae_log_likelihood: a weighted BCE is not a likelihood, so a forward that recorded WBCE takes the plain
+// BCE instantiation here (and no weighted per-sample kernel exists)
+template <typename F> static int pick_recon_per_sample(vae_ctx* c, F&& f) {
+    return pick_const<VAE_RECON_BCE, VAE_RECON_MSE>("reconstruction term", c->fwd.recon == VAE_RECON_WBCE ? VAE_RECON_BCE : c->fwd.recon, f);
 }
 
 // Bands per image of a row-streaming launch.  Its units are (image, band of rows / bands rows); they run in rounds of one unit
@@ -421,7 +426,7 @@ static ConvOutFwdMfmaArgs<T> convout_fwd_mfma_args(vae_ctx* c, const ConvOutArgs
     ConvOutFwdMfmaArgs<T> m; memset(&m, 0, sizeof(m)); m.fuse = f7; m.rev = c->knob_rev & 1;
     m.yf = reinterpret_cast<const T*>(a.yf); m.coef = a.coef; m.wt = a.wt; m.bias = a.bias; m.target = a.target;
     m.xhat = a.xhat; m.dlogit = a.dlogit; m.accum = a.accum; m.B = a.B; m.H = a.H; m.W = a.W; m.n_tiles = a.B * (a.H / 8) * (a.W / 32);
-    m.inv_n = a.inv_n; m.slope = a.slope; m.part = a.part; m.tB = a.tB;
+    m.inv_n = a.inv_n; m.slope = a.slope; m.recon_w = a.recon_w; m.part = a.part; m.tB = a.tB;
     return m;
 }
 
@@ -438,12 +443,12 @@ static int launch_convout_per_sample(vae_ctx* c, ConvOutArgs a, const BnFuse& f7
             const ConvOutFwdMfmaArgs<T> m = convout_fwd_mfma_args<T>(c, a, f7);
             c->ps_ntile = (H / 8) * (H / 32);
             const dim3 grid(std::min(m.n_tiles, c->knob_convout_grid));
-            return pick_recon(c, [&](auto R) { return launch("convout_fwd_mfma_kernel(per sample)", convout_fwd_mfma_kernel<T, decltype(R)::value, true>, grid, dim3(256), 0, st, m); });
+            return pick_recon_per_sample(c, [&](auto R) { return launch("convout_fwd_mfma_kernel(per sample)", convout_fwd_mfma_kernel<T, decltype(R)::value, true>, grid, dim3(256), 0, st, m); });
         }
     }
     c->ps_ntile = (H / 16) * (H / 32);
     const dim3 grid(B * (H / 16) * (H / 32));
-    return pick_recon(c, [&](auto R) { return launch("convout_fwd_kernel(per sample)", convout_fwd_kernel<T, decltype(R)::value, true>, grid, dim3(256), 0, st, a); });
+    return pick_recon_per_sample(c, [&](auto R) { return launch("convout_fwd_kernel(per sample)", convout_fwd_kernel<T, decltype(R)::value, true>, grid, dim3(256), 0, st, a); });
 }
 
 // decoder half of the forward (models.py:147-175): decoder_input -> 3x ConvT blocks -> final_layer
@@ -490,7 +495,7 @@ int decode_impl(vae_ctx* c, const float* z, int B, const float* params, float* b
         ConvOutArgs a;
         a.yf = c->lay[7].y; a.coef = c->lay[7].block; a.wt = c->wout_t; a.bias = params + c->poff[39]; a.target = x;
         a.xhat = xhat; a.dlogit = c->dlogit; a.accum = c->accum; a.B = B; a.H = H; a.W = H;
-        a.inv_n = (float)(1.0 / ((double)B * H * H)); a.slope = kSlope; a.part = nullptr; a.tB = 0;
+        a.inv_n = (float)(1.0 / ((double)B * H * H)); a.slope = kSlope; a.recon_w = (float)c->fwd.recon_param; a.part = nullptr; a.tB = 0;
         const bool mfma_out = sizeof(T) == 2 && c->use_mfma_convout && 64.0 * B * H * H < 4294967296.0;   // 32-bit byte offsets
         BnFuse f7;
         if (input_bn_fwd(c, 7, params, bn_running, nbt, train, mfma_out, &f7, st)) return -1;
@@ -774,7 +779,7 @@ static int backward_first(vae_ctx* c, const float* x, const float* params, float
                 ConvOutStreamArgs<T> m; m.fuse = c->fwd.pending_f7;
                 m.yf = reinterpret_cast<const T*>(c->lay[7].y); m.wt = c->wout_t; m.bias = params + c->poff[39]; m.target = c->fwd.x;
                 m.xhat = c->fwd.xhat; m.accum = c->accum; m.dz = reinterpret_cast<T*>(c->lay[7].dz); m.slab = a.slab; m.stat = a.stat;
-                m.B = B; m.H = H; m.inv_n = (float)(1.0 / ((double)B * H * H)); m.slope = kSlope; m.gmul = c->fwd.gmul;
+                m.B = B; m.H = H; m.inv_n = (float)(1.0 / ((double)B * H * H)); m.slope = kSlope; m.gmul = c->fwd.gmul; m.recon_w = (float)c->fwd.recon_param;
                 m.dbg = (c->dbg_buf && !strcmp(c->dbg_tag, "final_layer.3")) ? c->dbg_buf : nullptr;
                 m.nb = stream_bands(B, H, 16, 8, 2, 3);
                 if (c->knob_convout_bands > 0 && H % c->knob_convout_bands == 0 && (H / c->knob_convout_bands) % 2 == 0 && H / c->knob_convout_bands >= 8) m.nb = c->knob_convout_bands;
@@ -788,7 +793,7 @@ static int backward_first(vae_ctx* c, const float* x, const float* params, float
                 m.yf = reinterpret_cast<const T*>(c->lay[7].y); m.wt = c->wout_t; m.bias = params + c->poff[39]; m.target = c->fwd.x;
                 m.xhat = c->fwd.xhat; m.accum = c->accum; m.dz = reinterpret_cast<T*>(c->lay[7].dz); m.slab = a.slab; m.stat = a.stat;
                 m.B = B; m.H = H; m.W = H; m.n_tiles = B * (H / 8) * (H / 32);
-                m.inv_n = (float)(1.0 / ((double)B * H * H)); m.slope = kSlope; m.gmul = c->fwd.gmul; m.ablate = c->knob_ablate_f;
+                m.inv_n = (float)(1.0 / ((double)B * H * H)); m.slope = kSlope; m.gmul = c->fwd.gmul; m.recon_w = (float)c->fwd.recon_param; m.ablate = c->knob_ablate_f;
                 grid = std::min(m.n_tiles, c->knob_convout_step_grid);   // 512 resident (2 per CU by LDS): two full rounds
                 rc = pick_recon(c, [&](auto R) { return launch("convout_bwd_kernel", convout_step_mfma_kernel<T, decltype(R)::value>, dim3(grid), dim3(256), convout_step_lds(), st, m); });
                 c->fwd.convout_pending = 0;

@@ -219,6 +219,19 @@ class ReconMetricsAccumulator:
         return out
 
 
+def balanced_pos_weight(note_density, max_weight=64.0) -> float:
+    """The ``pos_weight`` of ``VanillaVAE`` that balances notes against silence: ``min(max_weight, (1 - d) / d)`` for a note
+    density ``d`` in [0, 1] (a fraction, as ``ReconMetricsAccumulator.compute()["note_density"]`` reports it; ``evaluate()``'s key
+    of the same name is a percentage).  ``d = 0`` gives ``max_weight``; a ``d`` outside [0, 1] (or NaN) raises ValueError.  A pure
+    host function: nothing touches the device."""
+    d, cap = float(note_density), float(max_weight)
+    if not 0.0 <= d <= 1.0:
+        raise ValueError(f"note_density must be a fraction in [0, 1], got {note_density!r}")
+    if not (math.isfinite(cap) and cap > 0.0):
+        raise ValueError(f"max_weight must be a finite number > 0, got {max_weight!r}")
+    return cap if d == 0.0 else min(cap, (1.0 - d) / d)
+
+
 def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nll_samples=0, latent_rolls=0, note_thresholds=None):
     """nll_samples = K > 0 adds ``nll`` (mean over the samples of -log p(x), importance-weighted with K draws) and ``elbo``
     (mean per-sample ELBO), both in nats per roll (VanillaVAE.log_likelihood); 0 leaves keys, values and printout as the
@@ -229,6 +242,8 @@ def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nl
     printed ranges come from it) and adds ``bce`` (nats per cell, the ELBO's reconstruction term), ``precision``, ``recall``, ``f1``
     (percent, a note being a cell >= 0.5 in the stimulus and >= note_thresholds[0] in the output), ``note_density`` (percent) and,
     with more than one threshold, ``best_f1`` (percent) and the ``best_threshold`` that gives it; None leaves everything as it is.
+    ``bce`` is the UNWEIGHTED term whatever the model's ``pos_weight`` is (as ``nll`` / ``elbo`` are the unweighted Bernoulli), so
+    runs trained with different weights stay comparable.
     Under torch.distributed each rank reports its own shard."""
     notes = None if note_thresholds is None else ReconMetricsAccumulator(note_thresholds, device=device)
     if isinstance(latent_rolls, bool) or int(latent_rolls) != latent_rolls or latent_rolls < 0:

@@ -26,6 +26,20 @@ Deviations from the reference, all explicit:
     ``F.mse_loss(xhat, x)`` - a Gaussian likelihood for velocity-valued rolls
     with targets anywhere in [0, 1].  ``model.recon_loss`` may be reassigned; it
     is read at every forward and fused step.  ``loss()`` keys are unchanged.
+  * ``pos_weight=w`` (keyword-only; default ``None`` = off) weights the BCE
+    term against the sparsity of pianorolls:
+    ``F.binary_cross_entropy(xhat, x, weight=1 + (w - 1) * x)``, the mean still
+    over B*H*W.  For 0/1 rolls this is ``BCEWithLogitsLoss(pos_weight=w)``.
+    For velocity rolls the weight grows with how much of a note the cell is
+    and the per-cell optimum stays ``xhat = x`` (weighting only the positive
+    log term would move it).  A finite number in (0, 1024], not with
+    ``recon_loss="mse"``; ``evaluation.balanced_pos_weight`` derives one from
+    a note density.  Read at every forward and fused step like ``recon_loss``;
+    a forward's ``loss()`` and backward use the weight it ran with.
+    ``log_likelihood`` ignores it (a weighted BCE is not a likelihood) and
+    ``evaluate()``'s ``bce`` stays unweighted.  ``pos_weight=1`` gives the bits
+    of plain BCE.  f16 storage: the power-of-two gradient scale is lowered
+    by ``2**ceil(log2 w)`` for ``w > 1`` (csrc/vae_ctx.h: set_grad_scale).
   * ``kl_free_bits`` / ``kl_capacity`` (keyword-only; default off, the
     reference's plain KL) replace the KL term of the ELBO by
     ``sum_d max(kl_d, kl_free_bits)`` (Kingma et al. 2016; ``kl_d`` the batch
@@ -45,6 +59,16 @@ Deviations from the reference, all explicit:
     forward and fused step; batches of at most 4096.  ``total_correlation()``
     returns the value of the last forward.  Data parallel: TC is over the
     replica's OWN batch, as ``kl_d`` and the BatchNorm statistics are.
+
+  Reconstruction term of ``loss = reconstruction + kld_weight * T`` (mean over B*H*W):
+
+    ====================  ===============================
+    option                reconstruction
+    ====================  ===============================
+    (none)                bce(xhat, x)
+    ``recon_loss="mse"``  (xhat - x)^2
+    ``pos_weight=w``      (1 + (w - 1) x) * bce(xhat, x)
+    ====================  ===============================
 
   KL term ``T`` of ``loss = reconstruction + kld_weight * T``:
 
@@ -82,6 +106,19 @@ def _recon_kind(name) -> int:
     if kind is None:
         raise ValueError(f"recon_loss must be one of {sorted(_RECON)}, got {name!r}")
     return kind
+
+
+def _recon_setting(recon_loss, pos_weight=None) -> tuple[int, float]:
+    """(VAE_RECON_* kind, parameter) of the recon_loss / pos_weight pair; ValueError on anything the library would refuse."""
+    kind = _recon_kind(recon_loss)
+    if pos_weight is None:
+        return kind, 0.0
+    w = pos_weight
+    if isinstance(w, bool) or not isinstance(w, (int, float)) or not math.isfinite(w) or not 0 < w <= _lib.POS_WEIGHT_MAX:
+        raise ValueError(f"pos_weight must be None or a finite number in (0, {_lib.POS_WEIGHT_MAX:g}], got {pos_weight!r}")
+    if kind != _lib.RECON_BCE:
+        raise ValueError('pos_weight weights the BCE term: it cannot be combined with recon_loss="mse"')
+    return _lib.RECON_WBCE, float(w)
 
 
 def _kl_objective(free_bits, capacity, tc_weight=None) -> tuple[int, float]:
@@ -124,13 +161,13 @@ class _Context:
         self.handle = _lib.lib().vae_create(img_size, latent_dim, max_batch, dtype, int(generalised))
         if not self.handle:
             raise _lib.VaeLibError("vae_create: " + _lib.lib().vae_last_error().decode())
-        self.recon = _lib.RECON_BCE     # the library's default (vae_set_recon_loss)
+        self.recon = (_lib.RECON_BCE, 0.0)   # the library's default (vae_set_recon_loss_ex): kind, parameter
         self.kl = (_lib.KL_PLAIN, 0.0)  # the library's default (vae_set_kl_objective)
 
-    def set_recon(self, kind: int):
-        if kind != self.recon:
-            _lib.check(_lib.lib().vae_set_recon_loss(self.handle, kind), "vae_set_recon_loss")
-            self.recon = kind
+    def set_recon(self, recon: tuple[int, float]):
+        if recon != self.recon:         # (kind or weight changed; never for a model that stays with the default)
+            _lib.check(_lib.lib().vae_set_recon_loss_ex(self.handle, recon[0], recon[1]), "vae_set_recon_loss_ex")
+            self.recon = recon
 
     def set_kl(self, kl: tuple[int, float]):
         if kl != self.kl:               # (never for a model that leaves both options off: no call beyond the library's default)
@@ -237,14 +274,15 @@ class _GenericELBO(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xhat, target, mu, lv, kld_weight, recon, kl=(_lib.KL_PLAIN, 0.0)):
+        kind, param = recon if isinstance(recon, tuple) else (recon, 0.0)   # (VAE_RECON_* kind, its parameter)
         xhat, target, mu, lv = (t.contiguous().float() for t in (xhat, target, mu, lv))
         out3 = torch.empty(3, device=xhat.device, dtype=torch.float32)
         gx, gm, gl = torch.empty_like(xhat), torch.empty_like(mu), torch.empty_like(lv)
         with torch.cuda.device(xhat.device):
-            _lib.check(_lib.lib().vae_elbo_generic_kl(xhat.data_ptr(), target.data_ptr(), mu.data_ptr(), lv.data_ptr(),
-                                                     xhat.numel(), mu.shape[0], mu.shape[1], float(kld_weight), int(recon),
-                                                     int(kl[0]), float(kl[1]), out3.data_ptr(), gx.data_ptr(), gm.data_ptr(),
-                                                     gl.data_ptr(), _stream_ptr(xhat.device)), "vae_elbo_generic_kl")
+            _lib.check(_lib.lib().vae_elbo_generic_w(xhat.data_ptr(), target.data_ptr(), mu.data_ptr(), lv.data_ptr(),
+                                                    xhat.numel(), mu.shape[0], mu.shape[1], float(kld_weight), int(kind), float(param),
+                                                    int(kl[0]), float(kl[1]), out3.data_ptr(), gx.data_ptr(), gm.data_ptr(),
+                                                    gl.data_ptr(), _stream_ptr(xhat.device)), "vae_elbo_generic_w")
         ctx.save_for_backward(gx, gm, gl)
         ctx.mark_non_differentiable(out3)
         return out3[0].clone(), out3
@@ -274,6 +312,7 @@ class VanillaVAE(nn.Module):
         kl_free_bits: float = 0.0,
         kl_capacity: float | None = None,
         tc_weight: float | None = None,
+        pos_weight: float | None = None,
     ):
         super().__init__()
         if in_channels != 1:
@@ -295,8 +334,9 @@ class VanillaVAE(nn.Module):
         if compute_dtype not in _DTYPES:
             raise ValueError(f"compute_dtype must be one of {sorted(_DTYPES)}")
         self.compute_dtype = compute_dtype
-        _recon_kind(recon_loss)
+        _recon_setting(recon_loss, pos_weight)
         self.recon_loss = recon_loss
+        self.pos_weight = pos_weight
         _kl_objective(kl_free_bits, kl_capacity, tc_weight)
         self.kl_free_bits = kl_free_bits
         self.kl_capacity = kl_capacity
@@ -470,7 +510,7 @@ class VanillaVAE(nn.Module):
                 if getattr(self, "_want_lib_comm", False):
                     self._init_library_comm()
             self._max_batch = need
-        self._ctx.set_recon(_recon_kind(self.recon_loss))
+        self._ctx.set_recon(_recon_setting(self.recon_loss, getattr(self, "pos_weight", None)))
         tcw = getattr(self, "tc_weight", None)
         if self.kl_capacity is not None or self.kl_free_bits != 0.0 or tcw is not None or self._ctx.kl[0] != _lib.KL_PLAIN:
             self._ctx.set_kl(_kl_objective(self.kl_free_bits, self.kl_capacity, tcw))
@@ -750,7 +790,8 @@ class VanillaVAE(nn.Module):
             log_likelihood[b]  = logsumexp_k log_weights[k, b] - log K
             elbo[b]            = mean_k log p(x_b|z_kb) - KL(q(z|x_b) || N(0, I))
         p(x|z) follows ``recon_loss``: "bce" - Bernoulli (normalised only for 0/1 targets), "mse" - Gaussian with variance
-        1/2, whose negative log-likelihood is the summed squared error plus (H*W/2) log(pi).
+        1/2, whose negative log-likelihood is the summed squared error plus (H*W/2) log(pi).  ``pos_weight`` is ignored: a
+        weighted BCE is not a likelihood, the estimate stays the unweighted Bernoulli.
 
         Always in eval semantics (BatchNorm on the running statistics, which are read and never written), whatever
         ``self.training`` is; not differentiable.  The training noise seeds are untouched.  ``eps`` [K, B, latent_dim]
@@ -838,7 +879,8 @@ class VanillaVAE(nn.Module):
                                  "is evaluated at z = mu + eps * exp(log_var / 2) and only the model's own forward holds its eps "
                                  "(pass the forward's own output, or use vae_total_correlation with the eps)")
             loss, out3 = _GenericELBO.apply(output["output"], output["input"], output["encoded"]["mu"],
-                                            output["encoded"]["log_var"], self.kld_weight, _recon_kind(self.recon_loss),
+                                            output["encoded"]["log_var"], self.kld_weight,
+                                            _recon_setting(self.recon_loss, getattr(self, "pos_weight", None)),
                                             _kl_objective(self.kl_free_bits, self.kl_capacity))
         return LossOutput(loss=loss, reconstruction_loss=out3[1].detach(), kld_loss=out3[2].detach())
 

@@ -304,6 +304,8 @@ def train_one_epoch(config, model, optimizer, scheduler, criterion, dataloader, 
         model.kl_free_bits = config.kl_free_bits
     if getattr(config, "kl_tc_weight", None) is not None:
         model.tc_weight = config.kl_tc_weight
+    if getattr(config, "recon_pos_weight", None) is not None:   # positive-class weight of the BCE term (VanillaVAE.pos_weight), both step paths
+        model.pos_weight = config.recon_pos_weight
     n_batches = len(dataloader)
     in_flight = deque()   # pinned host batches a device kernel may still be reading, with the event that follows that kernel
     for batch_idx, (stimuli, y_true) in enumerate(dataloader):
