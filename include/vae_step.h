@@ -393,6 +393,40 @@ int vae_synth_pianoroll(float* x, int batch, int img_size, uint64_t seed, vae_st
  * pageable host memory is refused.  n_cells = B*H*W, a multiple of 8. */
 int vae_expand_stimuli(const void* src, int kind, float* dst, int64_t n_cells, vae_stream_t stream);
 
+/* One training batch out of a resident set of pianorolls, augmented on the way: picks `batch` rolls, cuts a window of `w` time
+ * steps out of each, shifts it in time and transposes it in pitch, and writes the float32 batch [batch,1,h,w] the step reads.
+ * The reference's data_transformations.get_transform (RandomCrop for training, CenterCrop for evaluation) as one launch.
+ * src holds n_rolls rolls of h rows (pitch) by src_w columns (time), row-major.  kind 0: one byte per cell, dst = (float)v * scale;
+ * kind 1: bit planes, most significant bit first (numpy.packbits order), src_w/8 bytes per row, cells 0.f / 1.f; kind 2: float32
+ * cells, copied (scale is ignored by kinds 1 and 2).  src is device memory or PINNED host memory read in place, as for
+ * vae_expand_stimuli; pageable host memory is refused.
+ * With i = index ? index[b] : first + b, for every output cell
+ *     dst[b,0,y,x] = S(i, y - dy_b, c0_b + x)   if 0 <= i < n_rolls, 0 <= y - dy_b < h and 0 <= c0_b + x < src_w, else 0
+ * dy is clamped to [-h, h] and c0 to [-w, src_w] first (beyond those the roll is all zero anyway).  c0 is crop offset and time
+ * shift in one: a shift inside a longer roll shows the neighbouring content, zeros appear only past the roll's ends; pitch is always
+ * zero-filled.  An index outside [0, n_rolls) gives a zero roll: the guards live in the kernel, which forms no address outside
+ * src[0 .. n_rolls*h*row_bytes) whatever index and params hold (device-resident indices cannot be validated on the host without
+ * a synchronisation).
+ * (dy_b, c0_b) = params[b] when params (device, [batch,2] int32) is given.  With params NULL they are drawn in the kernel from the
+ * counter generator (oracle.counter_uniform) on stream 901, for sample b with counter k = counter0 + b * counter_stride, P =
+ * max_pitch_shift, T = max_time_shift and slack s = src_w - w:
+ *     dy = (int)(u(2k) * (2P+1)) - P
+ *     c0 = (int)(u(2k+1) * (s + 2T + 1)) - T            crop_mode 0 (random window)
+ *     c0 = s/2 + (int)(u(2k+1) * (2T+1)) - T            crop_mode 1 (centre window; with P = T = 0 nothing is random)
+ * counter_stride lets data-parallel ranks that take every world-th position of one global permutation number their samples by
+ * that global position (counter0 = position of the batch's first sample, counter_stride = world): a roll's augmentation is then a
+ * function of (seed, position) alone, whatever the batch size and the number of ranks.  A single process passes 1.
+ * vae_augment_params writes exactly these draws to params, unclamped, for inspection.
+ * Returns -1 before anything is enqueued for: null src or dst; kind outside 0..2; h <= 0; batch < 0 (batch == 0 returns 0 and
+ * launches nothing); w or src_w not a positive multiple of 8 (or above 2^30); src_w < w; n_rolls <= 0 or n_rolls * h * row_bytes
+ * beyond 2^62; a negative max_*_shift (or one above 2^24); crop_mode outside 0..1; a non-finite scale; dst not 16-byte, index not
+ * 8-byte, params or a kind-2 src not 4-byte aligned; a src that is neither device nor pinned host memory. */
+int vae_gather_rolls(const void* src, int kind, int64_t n_rolls, int h, int src_w, const int64_t* index, int64_t first,
+                     const int32_t* params, uint64_t seed, uint64_t counter0, uint64_t counter_stride, int max_pitch_shift,
+                     int max_time_shift, int crop_mode, float scale, float* dst, int batch, int w, vae_stream_t stream);
+int vae_augment_params(int32_t* params, int batch, int src_w, int w, uint64_t seed, uint64_t counter0, uint64_t counter_stride,
+                       int max_pitch_shift, int max_time_shift, int crop_mode, vae_stream_t stream);
+
 /* Per-kernel timing for bench.py's roofline line: when enabled every launch of the step is
  * bracketed by HIP events on the launch stream; the report is a JSON array with, per kernel name,
  * calls, total ms, and total ALGORITHMIC bytes / flops (operand tensors once). */

@@ -17,7 +17,8 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "6" if _os.environ.get("VAE_DP_OVERL
 
 from .types_helpers import EncoderOutput, LossOutput, ModelOutput  # noqa: F401,E402
 
-__all__ = ["VanillaVAE", "FusedAdamW", "train_one_epoch", "build_optimizer", "SyntheticPianorollLoader"]
+__all__ = ["VanillaVAE", "FusedAdamW", "train_one_epoch", "build_optimizer", "SyntheticPianorollLoader", "PianorollDataset",
+           "DevicePianorollLoader", "epoch_indices", "gather_rolls", "augmentation_params"]
 
 
 def __getattr__(name):
@@ -36,4 +37,7 @@ def __getattr__(name):
     if name in ("train_one_epoch", "build_optimizer", "SyntheticPianorollLoader", "allreduce_gradients", "fused_step"):
         from . import train
         return getattr(train, name)
+    if name in ("PianorollDataset", "DevicePianorollLoader", "epoch_indices", "gather_rolls", "augmentation_params"):
+        from . import data
+        return getattr(data, name)
     raise AttributeError(name)

@@ -28,6 +28,13 @@ KL_TC = 3
 TC_MAX_BATCH = 4096   # include/vae_step.h: VAE_KL_TC, vae_total_correlation
 RECON_METRICS_MAX_THRESHOLDS = 8   # include/vae_step.h: vae_recon_metrics
 COMM_ID_BYTES = 128
+ROLLS_BYTES, ROLLS_BITS, ROLLS_F32 = 0, 1, 2   # include/vae_step.h: the source kinds of vae_gather_rolls
+CROP_RANDOM, CROP_CENTRE = 0, 1
+AUGMENT_STREAM = 901                           # counter-generator stream of the augmentation draws
+# csrc/augment.cuh, vae_gather_rolls: lanes per workgroup, the cap on workgroups, cells per lane, the most lanes along a row.  A
+# workgroup is a tile of TX lanes along a row (the smallest power of two >= w/8, at most 64) by 256/TX rows; the grid's x walks the
+# row tiles of one roll (capped), its y the samples (what the cap leaves, at least 1); past either, and past TX, a stride loop
+GATHER_THREADS, GATHER_MAX_BLOCKS, GATHER_CELLS_PER_LANE, GATHER_MAX_ROW_LANES = 256, 2048, 8, 64
 GRAD_CLIP_SCRATCH_BYTES = 8192   # include/vae_step.h: VAE_GRAD_CLIP_SCRATCH_BYTES
 
 PARAM_NAMES = (
@@ -112,6 +119,8 @@ def lib():
                                                f32, f64, i32, p, p, p, p, i32, p, p, p, p, p, p])
     _sig(L.vae_synth_pianoroll, i32, [p, i32, i32, u64, p])
     _sig(L.vae_expand_stimuli, i32, [p, i32, p, i64, p])
+    _sig(L.vae_gather_rolls, i32, [p, i32, i64, i32, i32, p, i64, p, u64, u64, u64, i32, i32, i32, f32, p, i32, i32, p])
+    _sig(L.vae_augment_params, i32, [p, i32, i32, i32, u64, u64, u64, i32, i32, i32, p])
     _sig(L.vae_profile, i32, [p, i32])
     _sig(L.vae_profile_report, i32, [p, C.c_char_p, i64])
     _sig(L.vae_profile_sequence, i32, [p, C.c_char_p, i64])
@@ -134,7 +143,7 @@ EXPORTS = [
     "vae_comm_destroy", "vae_allreduce_grads", "vae_broadcast_state", "vae_adamw_step", "vae_train_step", "vae_train_step_fused",
     "vae_grad_norm", "vae_adamw_step_clipped", "vae_train_step_fused_clipped", "vae_synth_pianoroll", "vae_expand_stimuli", "vae_profile",
     "vae_profile_report", "vae_profile_sequence", "vae_profile_timeline", "vae_debug_stamps", "vae_debug_tensor",
-    "vae_selftest_tr16", "vae_set_option", "vae_option_info",
+    "vae_selftest_tr16", "vae_set_option", "vae_option_info", "vae_gather_rolls", "vae_augment_params",
 ]
 
 

@@ -1,8 +1,10 @@
 // Context-free utilities of the C ABI (include/vae_step.h): data synthesis and stimulus expansion, the ds_read_b64_tr_b16 self-test,
-// latent diagnostics and reconstruction metrics.  Nothing here touches a context or shares a helper with vae_api.hip.
+// latent diagnostics, reconstruction metrics and the resident-pianoroll gather with its augmentation.  Nothing here touches a context
+// or shares a helper with vae_api.hip.
 #include "vae_ctx.h"
 #include "latent_stats.cuh"
 #include "recon_metrics.cuh"
+#include "augment.cuh"
 
 // data_generators.py:45-77 restated with the counter generator (stream 777); one workgroup per image
 __global__ void synth_pianoroll_kernel(float* x, int H, unsigned long long seed, int max_lines) {
@@ -48,25 +50,80 @@ __global__ void expand_bits_kernel(const uint8_t* __restrict__ src, float* __res
         *reinterpret_cast<f32x4*>(dst + 8 * i + 4) = f32x4{(float)((w >> 3) & 1u), (float)((w >> 2) & 1u), (float)((w >> 1) & 1u), (float)(w & 1u)};
     }
 }
+// The address the device uses for a source that a kernel reads in place: device memory as is, pinned host memory through its
+// mapping; anything else (pageable host memory) is refused under `what` - a kernel must not dereference it - and null returned.
+static const void* device_source(const char* what, const void* src) {
+    hipPointerAttribute_t at; memset(&at, 0, sizeof(at));
+    if (hipPointerGetAttributes(&at, src) != hipSuccess) (void)hipGetLastError();
+    else if (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged) return src;
+    else if (at.type == hipMemoryTypeHost && at.devicePointer) return at.devicePointer;
+    vae_set_error(what, "the source is neither device nor pinned host memory");
+    return nullptr;
+}
 extern "C" int vae_expand_stimuli(const void* src, int kind, float* dst, int64_t n_cells, vae_stream_t stream) {
     if (!src || !dst) return vae_set_error("vae_expand_stimuli", "null pointer");
     if (kind != 0 && kind != 1) return vae_set_error("vae_expand_stimuli", "kind must be 0 (bytes) or 1 (bit planes)");
     if (n_cells < 0 || n_cells % 8) return vae_set_error("vae_expand_stimuli", "the number of cells must be a multiple of 8");
     if (n_cells == 0) return 0;
-    // the address the device uses for the source: device memory as is, pinned host memory through its mapping; anything else
-    // (pageable host memory) is refused - a kernel must not dereference it
-    hipPointerAttribute_t at; memset(&at, 0, sizeof(at));
-    if (hipPointerGetAttributes(&at, src) != hipSuccess) { (void)hipGetLastError(); return vae_set_error("vae_expand_stimuli", "the source is neither device nor pinned host memory"); }
-    const void* dsrc = nullptr;
-    if (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged) dsrc = src;
-    else if (at.type == hipMemoryTypeHost && at.devicePointer) dsrc = at.devicePointer;
-    else return vae_set_error("vae_expand_stimuli", "the source is neither device nor pinned host memory");
+    const void* dsrc = device_source("vae_expand_stimuli", src);
+    if (!dsrc) return -1;
     if ((reinterpret_cast<uintptr_t>(dsrc) & 3) || (reinterpret_cast<uintptr_t>(dst) & 15)) return vae_set_error("vae_expand_stimuli", "source must be 4-byte, destination 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const long n = n_cells / (kind == 0 ? 4 : 8);   // words of four byte cells, or bytes of eight bit cells
     const dim3 grid((unsigned)std::min<long>((n + 255) / 256, 2048));
     if (kind == 0) return launch("expand_stimuli_kernel", expand_bytes_kernel, grid, dim3(256), 0, st, reinterpret_cast<const uint32_t*>(dsrc), dst, n);
     return launch("expand_stimuli_kernel", expand_bits_kernel, grid, dim3(256), 0, st, reinterpret_cast<const uint8_t*>(dsrc), dst, n);
+}
+
+// Resident pianorolls -> one augmented float32 batch (augment.cuh); the draws alone for inspection.  Both are one launch.
+static const char* augment_refusal(int batch, int src_w, int w, int P, int T, int crop_mode) {
+    if (batch < 0) return "batch must be >= 0";
+    if (w <= 0 || w % 8 || src_w <= 0 || src_w % 8 || src_w > (1 << 30)) return "w and src_w must be positive multiples of 8 (at most 2^30)";
+    if (src_w < w) return "src_w must be >= w";
+    if (P < 0 || T < 0 || P > (1 << 24) || T > (1 << 24)) return "max_pitch_shift and max_time_shift must be in [0, 2^24]";
+    if (crop_mode != 0 && crop_mode != 1) return "crop_mode must be 0 (random) or 1 (centre)";
+    return nullptr;
+}
+extern "C" int vae_gather_rolls(const void* src, int kind, int64_t n_rolls, int h, int src_w, const int64_t* index, int64_t first,
+                                const int32_t* params, uint64_t seed, uint64_t counter0, uint64_t counter_stride, int max_pitch_shift,
+                                int max_time_shift, int crop_mode, float scale, float* dst, int batch, int w, vae_stream_t stream) {
+    const char* what = "vae_gather_rolls";
+    if (!src || !dst) return vae_set_error(what, "null pointer (src, dst)");
+    if (kind < 0 || kind > 2) return vae_set_error(what, "kind must be 0 (bytes), 1 (bit planes) or 2 (float32)");
+    if (h <= 0) return vae_set_error(what, "h must be > 0");
+    if (const char* why = augment_refusal(batch, src_w, w, max_pitch_shift, max_time_shift, crop_mode)) return vae_set_error(what, why);
+    const int64_t row_bytes = kind == 1 ? src_w / 8 : (int64_t)src_w * (kind == 2 ? 4 : 1);
+    if (n_rolls <= 0 || n_rolls > ((int64_t)1 << 62) / ((int64_t)h * row_bytes)) return vae_set_error(what, "n_rolls must be > 0 (and the source below 2^62 bytes)");
+    if (!std::isfinite(scale)) return vae_set_error(what, "scale must be finite");
+    if ((reinterpret_cast<uintptr_t>(dst) & 15) || (reinterpret_cast<uintptr_t>(index) & 7) || (reinterpret_cast<uintptr_t>(params) & 3))
+        return vae_set_error(what, "dst must be 16-byte, index 8-byte, params 4-byte aligned");
+    if (batch == 0) return 0;
+    const void* dsrc = device_source(what, src);
+    if (!dsrc) return -1;
+    if (kind == 2 && (reinterpret_cast<uintptr_t>(dsrc) & 3)) return vae_set_error(what, "a float32 source must be 4-byte aligned");
+    GatherArgs a{dsrc, (long)n_rolls, h, src_w, reinterpret_cast<const long*>(index), (long)first, params, (unsigned long long)seed,
+                 (unsigned long long)counter0, (unsigned long long)counter_stride, max_pitch_shift, max_time_shift, crop_mode, scale, dst, batch, w, 0};
+    // workgroup tile: TX = 2^lg_tx lanes along a row (covering its w/8 work items where 64 lanes can) by AUG_THREADS / TX rows.
+    // grid x: row tiles of one roll, y: samples; at most AUG_MAX_BLOCKS workgroups, the rest is stride loops
+    int lg_tx = 0;
+    while ((1 << lg_tx) < w / 8 && lg_tx < 6) ++lg_tx;
+    const long rows = AUG_THREADS >> lg_tx;
+    const unsigned gx = (unsigned)std::min<long>((h + rows - 1) / rows, AUG_MAX_BLOCKS);
+    const dim3 grid(gx, (unsigned)std::min<long>(batch, std::max<long>(1, AUG_MAX_BLOCKS / gx)));
+    a.lg_tx = lg_tx;
+    return pick_const<0, 1, 2>("gather_rolls_kernel", kind, [&](auto K) {
+        return launch("gather_rolls_kernel", gather_rolls_kernel<decltype(K)::value>, grid, dim3(AUG_THREADS), 0, (hipStream_t)stream, a); });
+}
+extern "C" int vae_augment_params(int32_t* params, int batch, int src_w, int w, uint64_t seed, uint64_t counter0, uint64_t counter_stride,
+                                  int max_pitch_shift, int max_time_shift, int crop_mode, vae_stream_t stream) {
+    const char* what = "vae_augment_params";
+    if (!params) return vae_set_error(what, "null pointer (params)");
+    if (const char* why = augment_refusal(batch, src_w, w, max_pitch_shift, max_time_shift, crop_mode)) return vae_set_error(what, why);
+    if (reinterpret_cast<uintptr_t>(params) & 3) return vae_set_error(what, "params must be 4-byte aligned");
+    if (batch == 0) return 0;
+    const dim3 grid((unsigned)std::min<long>(((long)batch + AUG_THREADS - 1) / AUG_THREADS, AUG_MAX_BLOCKS));
+    return launch("augment_params_kernel", augment_params_kernel, grid, dim3(AUG_THREADS), 0, (hipStream_t)stream, params, batch, src_w - w,
+                  (unsigned long long)seed, (unsigned long long)counter0, (unsigned long long)counter_stride, max_pitch_shift, max_time_shift, crop_mode);
 }
 
 // Latent diagnostics (latent_stats.cuh).  Launches: prep (tables, z), joint and dims pairwise kernels over split component ranges,

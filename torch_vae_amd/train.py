@@ -20,6 +20,7 @@ from contextlib import nullcontext
 import torch
 import torch.distributed as dist
 
+from .data import DevicePianorollLoader
 from .models import VanillaVAE
 from .optim import FusedAdamW
 
@@ -306,6 +307,8 @@ def train_one_epoch(config, model, optimizer, scheduler, criterion, dataloader, 
         model.tc_weight = config.kl_tc_weight
     if getattr(config, "recon_pos_weight", None) is not None:   # positive-class weight of the BCE term (VanillaVAE.pos_weight), both step paths
         model.pos_weight = config.recon_pos_weight
+    if isinstance(dataloader, DevicePianorollLoader):   # its order and augmentation draws are functions of (seed, epoch)
+        dataloader.set_epoch(epoch)
     n_batches = len(dataloader)
     in_flight = deque()   # pinned host batches a device kernel may still be reading, with the event that follows that kernel
     for batch_idx, (stimuli, y_true) in enumerate(dataloader):
