@@ -427,6 +427,31 @@ int vae_gather_rolls(const void* src, int kind, int64_t n_rolls, int h, int src_
 int vae_augment_params(int32_t* params, int batch, int src_w, int w, uint64_t seed, uint64_t counter0, uint64_t counter_stride,
                        int max_pitch_shift, int max_time_shift, int crop_mode, vae_stream_t stream);
 
+/* Note events out of float pianorolls, the other end of vae_gather_rolls: what a decoded batch holds as notes, and the cleaned
+ * batch as bit planes.  rolls is [n][h][w] float32, pitch rows by time columns, row-major (the model's [B,1,H,W] output as it is).
+ * All comparisons are float32 against float32; a NaN cell compares false with everything.  For each row (r, p), over t = 0..w-1:
+ *   hysteresis  s[-1] = 0; s[t] = 1 if x[t] >= onset_threshold; s[t] = 0 if not (x[t] >= sustain_threshold) (a NaN is off);
+ *               otherwise s[t] = s[t-1].  sustain_threshold == onset_threshold is plain thresholding.
+ *   bridging    a maximal run of zeros in s of length <= max_gap with a one on both sides becomes ones; runs touching either end
+ *               of the row never do; max_gap = 0 changes nothing.
+ *   notes       the maximal runs of ones after bridging; runs shorter than min_duration are dropped.
+ *   event       of a kept run [t0, t0 + len): events[i] = (r, p, t0, len) and peaks[i] = max x[t] over the run, bridged cells
+ *               included and NaNs skipped - an exact value of the input, whatever the order.
+ * Events ascend by (roll, pitch, onset).  offsets[r] is the index of roll r's first event and offsets[n] the number of events; both
+ * are right whatever the capacity: events with index >= capacity are not written (no slot past the first `capacity` is touched).
+ * cleaned, [n][h][w/8] bytes, has bit t of row (r, p) set exactly for the cells of kept notes, most significant bit first
+ * (numpy.packbits order): the kind-1 source of vae_gather_rolls and vae_expand_stimuli.
+ * events and peaks may both be NULL (a count-only call: offsets alone, and cleaned when given); cleaned may be NULL.  No position
+ * depends on an atomic or on arrival order: repeated calls give the same bits.  Nothing synchronises with the host; the work space
+ * (one int32 per row, one int64 per 16384 rows) comes from the stream-ordered allocator.
+ * Returns -1 before anything is enqueued for: null rolls or offsets; exactly one of events and peaks null; n < 0 (n == 0 zeroes
+ * offsets[0] and returns 0); h < 1; w not a multiple of 8 in 8..65536; n * h >= 2^31; a non-finite threshold; sustain_threshold >
+ * onset_threshold; min_duration < 1; max_gap < 0; capacity < 0; rolls, events or peaks not 4-byte aligned; offsets not 8-byte
+ * aligned.  An event is one 16-byte store where events is 16-byte aligned. */
+int vae_extract_notes(const float* rolls, int64_t n, int h, int w, float onset_threshold, float sustain_threshold,
+                      int min_duration, int max_gap, int32_t* events /*[capacity][4]*/, float* peaks /*[capacity]*/,
+                      int64_t capacity, int64_t* offsets /*[n+1]*/, uint8_t* cleaned /*[n][h][w/8]*/, vae_stream_t stream);
+
 /* Per-kernel timing for bench.py's roofline line: when enabled every launch of the step is
  * bracketed by HIP events on the launch stream; the report is a JSON array with, per kernel name,
  * calls, total ms, and total ALGORITHMIC bytes / flops (operand tensors once). */

@@ -18,7 +18,8 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "6" if _os.environ.get("VAE_DP_OVERL
 from .types_helpers import EncoderOutput, LossOutput, ModelOutput  # noqa: F401,E402
 
 __all__ = ["VanillaVAE", "FusedAdamW", "train_one_epoch", "build_optimizer", "SyntheticPianorollLoader", "PianorollDataset",
-           "DevicePianorollLoader", "epoch_indices", "gather_rolls", "augmentation_params"]
+           "DevicePianorollLoader", "epoch_indices", "gather_rolls", "augmentation_params", "extract_notes", "binarize_rolls",
+           "events_to_lists"]
 
 
 def __getattr__(name):
@@ -40,4 +41,7 @@ def __getattr__(name):
     if name in ("PianorollDataset", "DevicePianorollLoader", "epoch_indices", "gather_rolls", "augmentation_params"):
         from . import data
         return getattr(data, name)
+    if name in ("extract_notes", "binarize_rolls", "events_to_lists", "interpolate_latents"):
+        from . import generation
+        return getattr(generation, name)
     raise AttributeError(name)

@@ -121,6 +121,7 @@ def lib():
     _sig(L.vae_expand_stimuli, i32, [p, i32, p, i64, p])
     _sig(L.vae_gather_rolls, i32, [p, i32, i64, i32, i32, p, i64, p, u64, u64, u64, i32, i32, i32, f32, p, i32, i32, p])
     _sig(L.vae_augment_params, i32, [p, i32, i32, i32, u64, u64, u64, i32, i32, i32, p])
+    _sig(L.vae_extract_notes, i32, [p, i64, i32, i32, f32, f32, i32, i32, p, p, i64, p, p, p])
     _sig(L.vae_profile, i32, [p, i32])
     _sig(L.vae_profile_report, i32, [p, C.c_char_p, i64])
     _sig(L.vae_profile_sequence, i32, [p, C.c_char_p, i64])
@@ -144,6 +145,7 @@ EXPORTS = [
     "vae_grad_norm", "vae_adamw_step_clipped", "vae_train_step_fused_clipped", "vae_synth_pianoroll", "vae_expand_stimuli", "vae_profile",
     "vae_profile_report", "vae_profile_sequence", "vae_profile_timeline", "vae_debug_stamps", "vae_debug_tensor",
     "vae_selftest_tr16", "vae_set_option", "vae_option_info", "vae_gather_rolls", "vae_augment_params",
+    "vae_extract_notes",
 ]
 
 

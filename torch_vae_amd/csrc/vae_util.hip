@@ -1,10 +1,11 @@
 // Context-free utilities of the C ABI (include/vae_step.h): data synthesis and stimulus expansion, the ds_read_b64_tr_b16 self-test,
-// latent diagnostics, reconstruction metrics and the resident-pianoroll gather with its augmentation.  Nothing here touches a context
-// or shares a helper with vae_api.hip.
+// latent diagnostics, reconstruction metrics, the resident-pianoroll gather with its augmentation and the note-event extraction.
+// Nothing here touches a context or shares a helper with vae_api.hip.
 #include "vae_ctx.h"
 #include "latent_stats.cuh"
 #include "recon_metrics.cuh"
 #include "augment.cuh"
+#include "note_events.cuh"
 
 // data_generators.py:45-77 restated with the counter generator (stream 777); one workgroup per image
 __global__ void synth_pianoroll_kernel(float* x, int H, unsigned long long seed, int max_lines) {
@@ -225,6 +226,52 @@ extern "C" int vae_recon_metrics(const float* xhat, const float* target, int64_t
         return launch("recon_metrics_fold_kernel", recon_metrics_fold_kernel, dim3(1 + (3 + ncnt + 3) / 4), dim3(RM_THREADS), 0, st, (long)rolls,
                       (long)nchunks, ncnt, (double)rolls * (double)roll_len, ps, pc, pr, roll_sums, reinterpret_cast<long long*>(roll_counts), totals,
                       reinterpret_cast<long long*>(total_counts), accumulate);
+    });
+}
+
+// Note events of float pianorolls (note_events.cuh).  Launches: the count per row, the one-workgroup scan (which also writes offsets),
+// the write of events, peaks and cleaned planes - skipped when no events are asked for (the count launch then writes the planes).  Work space: one int32 per row and one
+// int64 per scan tile, from the stream-ordered allocator; nothing is read back.
+extern "C" int vae_extract_notes(const float* rolls, int64_t n, int h, int w, float onset_threshold, float sustain_threshold,
+                                 int min_duration, int max_gap, int32_t* events, float* peaks, int64_t capacity, int64_t* offsets,
+                                 uint8_t* cleaned, vae_stream_t stream) {
+    const char* what = "vae_extract_notes";
+    if (!rolls || !offsets) return vae_set_error(what, "null pointer (rolls, offsets)");
+    if (!events != !peaks) return vae_set_error(what, "events and peaks must both be given or both be null");
+    if (n < 0) return vae_set_error(what, "n must be >= 0");
+    if (h < 1) return vae_set_error(what, "h must be >= 1");
+    if (w < 8 || w > NE_MAX_W || w % 8) return vae_set_error(what, "w must be a multiple of 8 in 8..65536");
+    if (n > (int64_t)INT32_MAX / h) return vae_set_error(what, "n * h must stay below 2^31");
+    if (!std::isfinite(onset_threshold) || !std::isfinite(sustain_threshold)) return vae_set_error(what, "the thresholds must be finite");
+    if (sustain_threshold > onset_threshold) return vae_set_error(what, "sustain_threshold must be <= onset_threshold");
+    if (min_duration < 1) return vae_set_error(what, "min_duration must be >= 1");
+    if (max_gap < 0) return vae_set_error(what, "max_gap must be >= 0");
+    if (capacity < 0) return vae_set_error(what, "capacity must be >= 0");
+    if ((reinterpret_cast<uintptr_t>(rolls) | reinterpret_cast<uintptr_t>(peaks) | reinterpret_cast<uintptr_t>(events)) & 3)
+        return vae_set_error(what, "rolls, events and peaks must be 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(offsets) & 7) return vae_set_error(what, "offsets must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (n == 0) {
+        HIP_CHECK_RET(hipMemsetAsync(offsets, 0, sizeof(int64_t), st));
+        return 0;
+    }
+    const long nrows = (long)n * h;
+    const size_t cnt_bytes = ((size_t)nrows * sizeof(int) + 255) / 256 * 256, ntiles = (size_t)((nrows + NE_TILE - 1) >> NE_TILE_LG);
+    const dim3 grid((unsigned)((nrows + NE_ROWS - 1) / NE_ROWS)), blk(NE_THREADS);
+    const size_t lds = (size_t)NE_ROWS * ((w + 63) / 64) * sizeof(ne_u64);
+    return with_stream_scratch(cnt_bytes + ntiles * sizeof(long long), st, [&](char* base) -> int {
+        int* counts = reinterpret_cast<int*>(base);
+        long long* tile_base = reinterpret_cast<long long*>(base + cnt_bytes);
+        const bool planes_only = !events && cleaned;
+        if (pick_bool(planes_only, [&](auto P) {
+                return launch("note_count_kernel", note_count_kernel<decltype(P)::value>, grid, blk, lds, st, rolls, nrows, w, onset_threshold,
+                              sustain_threshold, min_duration, max_gap, counts, reinterpret_cast<unsigned char*>(cleaned)); })) return -1;
+        if (launch("note_scan_kernel", note_scan_kernel, dim3(1), dim3(NE_SCAN_THREADS), 0, st, counts, nrows, h, tile_base,
+                   reinterpret_cast<long long*>(offsets), (long)n)) return -1;
+        if (!events) return 0;
+        return launch("note_emit_kernel", note_emit_kernel, grid, blk, lds, st, rolls, nrows, h, w, onset_threshold, sustain_threshold,
+                      min_duration, max_gap, (const int*)counts, (const long long*)tile_base, reinterpret_cast<int*>(events), peaks,
+                      (long long)capacity, reinterpret_cast<unsigned char*>(cleaned));
     });
 }
 

@@ -232,7 +232,57 @@ def balanced_pos_weight(note_density, max_weight=64.0) -> float:
     return cap if d == 0.0 else min(cap, (1.0 - d) / d)
 
 
-def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nll_samples=0, latent_rolls=0, note_thresholds=None):
+def _count_note_matches(pred, ref, onset_tolerance):
+    """(notes_pred, notes_true, matched) of two host lists of (roll, pitch, onset, duration) rows sorted by (roll, pitch, onset)."""
+    i = j = matched = 0
+    while i < len(pred) and j < len(ref):
+        (ra, pa, ta), (rb, pb, tb) = pred[i][:3], ref[j][:3]
+        if (ra, pa) != (rb, pb):     # the row that is behind catches up
+            if (ra, pa) < (rb, pb):
+                i += 1
+            else:
+                j += 1
+        elif abs(ta - tb) <= onset_tolerance:
+            matched += 1
+            i += 1
+            j += 1
+        elif ta < tb:
+            i += 1
+        else:
+            j += 1
+    return len(pred), len(ref), matched
+
+
+def note_event_ratios(notes_pred, notes_true, matched) -> dict:
+    """The result of note_event_metrics from its three counts; a ratio with a zero denominator is 0.0."""
+    div = lambda a, b: a / b if b else 0.0
+    return {"notes_pred": int(notes_pred), "notes_true": int(notes_true), "matched": int(matched),
+            "note_precision": div(matched, notes_pred), "note_recall": div(matched, notes_true),
+            "note_f1": div(2 * matched, notes_pred + notes_true)}
+
+
+def _host_events(ev):
+    """An event list as host rows: a NoteEvents dict (the events written, at most ``total``), a tensor or anything array-like."""
+    if isinstance(ev, dict):
+        ev = ev["events"][:min(int(ev["total"]), ev["events"].shape[0])]
+    if isinstance(ev, torch.Tensor):
+        return ev.detach().reshape(-1, 4).cpu().tolist()
+    return [[int(v) for v in row] for row in ev]
+
+
+def note_event_metrics(pred, ref, *, onset_tolerance=1) -> dict:
+    """Note-onset scores of predicted against reference events (``generation.extract_notes`` results, or [N,4] event arrays sorted
+    by (roll, pitch, onset)): a predicted note is matched when a reference note of the same roll and pitch has its onset within
+    ``onset_tolerance`` steps, every note at most once (a two-pointer sweep within each row, which finds the most matches there
+    are).  Returns notes_pred, notes_true, matched, note_precision, note_recall, note_f1.  Runs on the host after one read-back
+    of each event array."""
+    if isinstance(onset_tolerance, bool) or int(onset_tolerance) != onset_tolerance or onset_tolerance < 0:
+        raise ValueError(f"onset_tolerance must be an integer >= 0, got {onset_tolerance}")
+    return note_event_ratios(*_count_note_matches(_host_events(pred), _host_events(ref), int(onset_tolerance)))
+
+
+def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nll_samples=0, latent_rolls=0, note_thresholds=None,
+             note_events=None):
     """nll_samples = K > 0 adds ``nll`` (mean over the samples of -log p(x), importance-weighted with K draws) and ``elbo``
     (mean per-sample ELBO), both in nats per roll (VanillaVAE.log_likelihood); 0 leaves keys, values and printout as the
     reference has them.  latent_rolls = R > 0 keeps the eval forward's own mu / log_var of the first R rolls (loader order)
@@ -244,7 +294,20 @@ def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nl
     with more than one threshold, ``best_f1`` (percent) and the ``best_threshold`` that gives it; None leaves everything as it is.
     ``bce`` is the UNWEIGHTED term whatever the model's ``pos_weight`` is (as ``nll`` / ``elbo`` are the unweighted Bernoulli), so
     runs trained with different weights stay comparable.
+    note_events = a dict of ``generation.extract_notes`` keywords (onset_threshold, sustain_threshold, min_duration, max_gap) plus
+    ``onset_tolerance`` (default 1) and ``target_threshold`` (default 0.5) extracts, for every batch, the note events of the
+    reconstruction with those keywords and of the stimuli by plain thresholding at ``target_threshold``, matches them
+    (note_event_metrics) and adds ``notes_pred``, ``notes_true``, ``matched`` (counts over the pass) and ``note_precision``,
+    ``note_recall``, ``note_f1`` (fractions); None leaves results and launches as they are.
     Under torch.distributed each rank reports its own shard."""
+    if note_events is not None:
+        from .generation import extract_notes
+        ne_kw = dict(note_events)
+        ne_tol, ne_tt = ne_kw.pop("onset_tolerance", 1), ne_kw.pop("target_threshold", 0.5)
+        unknown = set(ne_kw) - {"onset_threshold", "sustain_threshold", "min_duration", "max_gap"}
+        if unknown:
+            raise ValueError(f"note_events has unknown keys {sorted(unknown)}")
+        ne_counts = [0, 0, 0]
     notes = None if note_thresholds is None else ReconMetricsAccumulator(note_thresholds, device=device)
     if isinstance(latent_rolls, bool) or int(latent_rolls) != latent_rolls or latent_rolls < 0:
         raise ValueError(f"latent_rolls must be an integer >= 0, got {latent_rolls}")
@@ -276,6 +339,11 @@ def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nl
             nll_sum -= lk["log_likelihood"].sum()
             elbo_sum += lk["elbo"].sum()
         rec = output["output"]
+        if note_events is not None:
+            got = extract_notes(rec, **ne_kw)
+            want = extract_notes(stimuli.float().contiguous(), onset_threshold=ne_tt)
+            for k, c in enumerate(_count_note_matches(_host_events(got), _host_events(want), int(ne_tol))):
+                ne_counts[k] += c
         if notes is not None:
             notes.update(rec, stimuli if stimuli.dtype == torch.float32 else stimuli.float())
             n_seen += stimuli.shape[0]
@@ -316,10 +384,14 @@ def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nl
         ls = latent_statistics(torch.cat(lat_mu), torch.cat(lat_lv))
         for k in ("kl", "active_units", "mi", "tc", "dwkl"):
             results[k] = ls[k] if k == "active_units" else float(ls[k])
+    if note_events is not None:
+        results.update(note_event_ratios(*ne_counts))
     if verbosity >= 1:
         print(f"\n{partition_name} evaluation results:")
         for k, v in results.items():
-            if "count" in k or k == "active_units":
+            if k in ("note_precision", "note_recall", "note_f1"):
+                print(f"  {k + ' ':.<24s} {100.0 * v:6.2f} %")
+            elif "count" in k or k == "active_units" or k in ("notes_pred", "notes_true", "matched"):
                 print(f"  {k + ' ':.<21s}{v:7d}")
             elif "entropy" in k or k == "bce":
                 print(f"  {k + ' ':.<24s} {v:9.5f} nat")

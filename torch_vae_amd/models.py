@@ -916,6 +916,45 @@ class VanillaVAE(nn.Module):
         with torch.no_grad():
             return self.decode(z)
 
+    def sample_notes(self, num_samples: int, *, temperature: float = 1.0, seed: int | None = None, return_rolls: bool = False,
+                     **extract_kwargs):
+        """Generated music as notes: z = temperature * N(0, I) from a ``torch.Generator`` on the model's device (seeded with
+        ``seed`` when given), decoded with running statistics (eval mode, whatever mode the model is in; it is left in that
+        mode and nothing of it changes), then ``generation.extract_notes(rolls, **extract_kwargs)``.  Returns the NoteEvents,
+        with the decoded ``rolls`` [num_samples,1,H,W] added under that key when ``return_rolls``."""
+        from .generation import extract_notes
+        self._require_device()
+        dev = self._flat.device
+        g = torch.Generator(device=dev)
+        if seed is None:
+            g.seed()
+        else:
+            g.manual_seed(int(seed))
+        z = float(temperature) * torch.randn(int(num_samples), self.latent_dim, generator=g, device=dev, dtype=torch.float32)
+        with torch.no_grad():
+            rolls = self._run_decode(z, train=False)
+        out = extract_notes(rolls, **extract_kwargs)
+        if return_rolls:
+            out["rolls"] = rolls
+        return out
+
+    def interpolate(self, x_a: Tensor, x_b: Tensor, steps: int, mode: str = "slerp"):
+        """Paths between pairs of rolls in latent space: both batches [pairs,1,H,W] are encoded with running statistics (eval
+        mode, the model untouched), their posterior means interpolated over ``steps`` points (``generation.interpolate_latents``:
+        "slerp" spherical, falling back to linear where the angle is below 1e-6, or "lerp"; plain torch) and every point decoded.
+        Returns ``(rolls [pairs, steps, 1, H, W], z [pairs, steps, L])``."""
+        from .generation import interpolate_latents
+        self._require_device()
+        if x_a.shape != x_b.shape:
+            raise ValueError(f"x_a and x_b must have the same shape, got {tuple(x_a.shape)} and {tuple(x_b.shape)}")
+        with torch.no_grad():
+            mu_a = self._run_encode(x_a, train=False)[0]
+            mu_b = self._run_encode(x_b, train=False)[0]
+            z = interpolate_latents(mu_a.float(), mu_b.float(), steps, mode).contiguous()
+            pairs, nsteps, L = z.shape
+            rolls = self._run_decode(z.view(pairs * nsteps, L), train=False)
+        return rolls.view(pairs, nsteps, *rolls.shape[1:]), z
+
     def generate(self, x: Tensor, **kwargs) -> Tensor:
         """models.py:265-272."""
         return self.forward(x)["output"]

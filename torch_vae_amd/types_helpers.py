@@ -1,4 +1,6 @@
 """Dict shapes returned by the model (mirror of the reference's types_helpers.py:15-37)."""
+from __future__ import annotations
+
 from typing import TypedDict
 
 from torch import Tensor
@@ -59,3 +61,11 @@ class ReconMetricsOutput(TypedDict):
     roll_positives: Tensor    # [N] int64
     roll_tp: Tensor           # [N, T] int64
     roll_fp: Tensor           # [N, T] int64
+
+
+class NoteEvents(TypedDict):
+    events: Tensor            # [N, 4] int32: (roll, pitch, onset, duration), ascending by (roll, pitch, onset)
+    peaks: Tensor             # [N] float32: the largest input value over the note's cells (NaNs skipped), exact
+    offsets: Tensor           # [n + 1] int64: roll r's events are events[offsets[r]:offsets[r + 1]]
+    cleaned: Tensor | None    # [n, h, w/8] uint8: the kept cells as bit planes, numpy.packbits order
+    total: Tensor             # 0-d int64 view of offsets[n]: the number of events, whatever the capacity
