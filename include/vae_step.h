@@ -452,6 +452,39 @@ int vae_extract_notes(const float* rolls, int64_t n, int h, int w, float onset_t
                       int min_duration, int max_gap, int32_t* events /*[capacity][4]*/, float* peaks /*[capacity]*/,
                       int64_t capacity, int64_t* offsets /*[n+1]*/, uint8_t* cleaned /*[n][h][w/8]*/, vae_stream_t stream);
 
+/* Nearest rolls of query rolls under transposition and time shift: is a generated roll new, or a training roll played back?
+ * queries is [n_queries][h][w/8] and rolls [n_rolls][h][w/8] bytes, bit planes of h pitch rows by w time columns, most significant
+ * bit first (numpy.packbits order: the kind-1 source of vae_gather_rolls, the cleaned planes of vae_extract_notes).  Everything is
+ * integer and exact.  With P = max_pitch_shift and T = max_time_shift:
+ *   shifted candidate  C'(y, x) = C(y - dy, x - dt) if 0 <= y - dy < h and 0 <= x - dt < w, else 0 - what vae_gather_rolls returns
+ *                      for params (dy, c0 = -dt) at width w.  The window is dy in [-P, P], dt in [-T, T].
+ *   shift rank         rank 0 is (0, 0); ranks 1, 2, ... are the other (dy, dt) ascending by (dy, dt).
+ *   pair               d(q, c) = min over the window of popcount(q XOR C'); the pair's shift is the lowest-ranked one that reaches
+ *                      it (against an empty candidate every shift ties and (0, 0) wins); intersection = popcount(q AND C') there.
+ *   neighbours         of query i: the rolls j != exclude[i] (exclude may be NULL; an entry outside [0, n_rolls) excludes nothing)
+ *                      ascending by (d, j); the first k go to index, distance, shift (dy, dt) and intersection [i][0..k).
+ *                      Slots with no candidate left hold index -1, distance -1, shift (0, 0), intersection 0.
+ *   query_cells[i]     popcount(q_i).
+ * (The shifted neighbour has d + 2 * intersection - query_cells cells; the pair's Jaccard index is intersection / (d + intersection).)
+ * Two launches.  The first gives each workgroup a tile of queries and one of `splits` contiguous ranges of rolls and leaves the k
+ * best keys (d << 40 | j, with the shift rank) per (query, range) in work space from the stream-ordered allocator; the second merges
+ * the ranges per query, counts the intersections and writes the outputs.  Keys are unique, so a k-best list is a set: the result does
+ * not depend on arrival order or on splits (0: chosen from n_queries and n_rolls alone; 1..64: as given, for tests), and repeated
+ * calls give the same bits.  No atomics; nothing synchronises with the host.  No byte outside queries, rolls and the outputs is
+ * addressed, whatever exclude holds.
+ * Returns -1 before anything is enqueued for: a null queries, rolls or output pointer; n_queries < 0 (n_queries == 0 returns 0 and
+ * launches nothing); n_rolls outside 1..2^40; h < 1; w not a positive multiple of 32; a roll of more than 8192 bytes (h * w / 8;
+ * 256 x 256 fits); max_pitch_shift outside 0..h-1; max_time_shift outside 0..w-1; (2P+1)(2T+1) > 1023; k outside 1..32; splits
+ * outside 0..64 (or ceil(n_queries / 16) * splits >= 2^31); queries or rolls not 4-byte aligned; index or exclude not 8-byte aligned; distance, shift, intersection or
+ * query_cells not 4-byte aligned. */
+int vae_nearest_rolls(const uint8_t* queries /*[n_queries][h][w/8]*/, int n_queries,
+                      const uint8_t* rolls   /*[n_rolls][h][w/8]*/,   int64_t n_rolls, int h, int w,
+                      int max_pitch_shift, int max_time_shift, const int64_t* exclude /*[n_queries] or NULL*/,
+                      int k, int splits /*0 = chosen by the library*/,
+                      int64_t* index /*[n_queries][k]*/, int32_t* distance /*[n_queries][k]*/,
+                      int32_t* shift /*[n_queries][k][2]*/, int32_t* intersection /*[n_queries][k]*/,
+                      int32_t* query_cells /*[n_queries]*/, vae_stream_t stream);
+
 /* Per-kernel timing for bench.py's roofline line: when enabled every launch of the step is
  * bracketed by HIP events on the launch stream; the report is a JSON array with, per kernel name,
  * calls, total ms, and total ALGORITHMIC bytes / flops (operand tensors once). */

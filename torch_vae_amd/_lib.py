@@ -35,7 +35,11 @@ AUGMENT_STREAM = 901                           # counter-generator stream of the
 # workgroup is a tile of TX lanes along a row (the smallest power of two >= w/8, at most 64) by 256/TX rows; the grid's x walks the
 # row tiles of one roll (capped), its y the samples (what the cap leaves, at least 1); past either, and past TX, a stride loop
 GATHER_THREADS, GATHER_MAX_BLOCKS, GATHER_CELLS_PER_LANE, GATHER_MAX_ROW_LANES = 256, 2048, 8, 64
-GRAD_CLIP_SCRATCH_BYTES = 8192   # include/vae_step.h: VAE_GRAD_CLIP_SCRATCH_BYTES
+# csrc/nearest_rolls.cuh, vae_nearest_rolls: queries per workgroup and candidates per LDS tile (rolls of more than
+# NEAREST_TILE_ROLL_BYTES take tiles of NEAREST_LARGE_TILE of either), the largest roll, the caps on (2P+1)(2T+1), k and splits
+NEAREST_QUERY_TILE, NEAREST_CAND_TILE, NEAREST_TILE_ROLL_BYTES, NEAREST_LARGE_TILE = 16, 16, 4608, 8
+NEAREST_MAX_ROLL_BYTES, NEAREST_MAX_SHIFTS, NEAREST_MAX_K, NEAREST_MAX_SPLITS = 8192, 1023, 32, 64
+GRAD_CLIP_SCRATCH_BYTES = 8192  # include/vae_step.h: VAE_GRAD_CLIP_SCRATCH_BYTES
 
 PARAM_NAMES = (
     [f"encoder.{i}.{j}" for i in range(4) for j in ("0.weight", "0.bias", "1.weight", "1.bias")]
@@ -122,6 +126,7 @@ def lib():
     _sig(L.vae_gather_rolls, i32, [p, i32, i64, i32, i32, p, i64, p, u64, u64, u64, i32, i32, i32, f32, p, i32, i32, p])
     _sig(L.vae_augment_params, i32, [p, i32, i32, i32, u64, u64, u64, i32, i32, i32, p])
     _sig(L.vae_extract_notes, i32, [p, i64, i32, i32, f32, f32, i32, i32, p, p, i64, p, p, p])
+    _sig(L.vae_nearest_rolls, i32, [p, i32, p, i64, i32, i32, i32, i32, p, i32, i32, p, p, p, p, p, p])
     _sig(L.vae_profile, i32, [p, i32])
     _sig(L.vae_profile_report, i32, [p, C.c_char_p, i64])
     _sig(L.vae_profile_sequence, i32, [p, C.c_char_p, i64])
@@ -145,7 +150,7 @@ EXPORTS = [
     "vae_grad_norm", "vae_adamw_step_clipped", "vae_train_step_fused_clipped", "vae_synth_pianoroll", "vae_expand_stimuli", "vae_profile",
     "vae_profile_report", "vae_profile_sequence", "vae_profile_timeline", "vae_debug_stamps", "vae_debug_tensor",
     "vae_selftest_tr16", "vae_set_option", "vae_option_info", "vae_gather_rolls", "vae_augment_params",
-    "vae_extract_notes",
+    "vae_extract_notes", "vae_nearest_rolls",
 ]
 
 

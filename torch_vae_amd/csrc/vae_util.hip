@@ -1,11 +1,13 @@
 // Context-free utilities of the C ABI (include/vae_step.h): data synthesis and stimulus expansion, the ds_read_b64_tr_b16 self-test,
-// latent diagnostics, reconstruction metrics, the resident-pianoroll gather with its augmentation and the note-event extraction.
+// latent diagnostics, reconstruction metrics, the resident-pianoroll gather with its augmentation, the note-event extraction and
+// the nearest-roll search.
 // Nothing here touches a context or shares a helper with vae_api.hip.
 #include "vae_ctx.h"
 #include "latent_stats.cuh"
 #include "recon_metrics.cuh"
 #include "augment.cuh"
 #include "note_events.cuh"
+#include "nearest_rolls.cuh"
 
 // data_generators.py:45-77 restated with the counter generator (stream 777); one workgroup per image
 __global__ void synth_pianoroll_kernel(float* x, int H, unsigned long long seed, int max_lines) {
@@ -272,6 +274,57 @@ extern "C" int vae_extract_notes(const float* rolls, int64_t n, int h, int w, fl
         return launch("note_emit_kernel", note_emit_kernel, grid, blk, lds, st, rolls, nrows, h, w, onset_threshold, sustain_threshold,
                       min_duration, max_gap, (const int*)counts, (const long long*)tile_base, reinterpret_cast<int*>(events), peaks,
                       (long long)capacity, reinterpret_cast<unsigned char*>(cleaned));
+    });
+}
+
+// Nearest rolls under transposition and time shift (nearest_rolls.cuh).  Two launches: the search over (query tiles, splits), which
+// leaves one k-best list per (query, split) in work space from the stream-ordered allocator, and the merge, one wave per query, which
+// also counts the intersections and the query cells.  splits = 0: what brings the grid to 1024 workgroups, at most one split per
+// candidate tile and at most NR_MAX_SPLITS - a function of (n_queries, n_rolls) and the tile sizes alone.
+extern "C" int vae_nearest_rolls(const uint8_t* queries, int n_queries, const uint8_t* rolls, int64_t n_rolls, int h, int w,
+                                 int max_pitch_shift, int max_time_shift, const int64_t* exclude, int k, int splits, int64_t* index,
+                                 int32_t* distance, int32_t* shift, int32_t* intersection, int32_t* query_cells, vae_stream_t stream) {
+    const char* what = "vae_nearest_rolls";
+    const int P = max_pitch_shift, T = max_time_shift;
+    if (!queries || !rolls || !index || !distance || !shift || !intersection || !query_cells)
+        return vae_set_error(what, "null pointer (queries, rolls, index, distance, shift, intersection, query_cells)");
+    if (n_queries < 0) return vae_set_error(what, "n_queries must be >= 0");
+    if (n_rolls < 1 || n_rolls > ((int64_t)1 << NR_INDEX_BITS)) return vae_set_error(what, "n_rolls must be in 1..2^40");
+    if (h < 1) return vae_set_error(what, "h must be >= 1");
+    if (w < 32 || w % 32) return vae_set_error(what, "w must be a positive multiple of 32");
+    if ((int64_t)h * (w / 8) > NR_MAX_ROLL_BYTES) return vae_set_error(what, "a roll (h * w / 8 bytes) must fit 8192 bytes");
+    if (P < 0 || P >= h) return vae_set_error(what, "max_pitch_shift must be in 0..h-1");
+    if (T < 0 || T >= w) return vae_set_error(what, "max_time_shift must be in 0..w-1");
+    if ((int64_t)(2 * P + 1) * (2 * T + 1) > NR_MAX_SHIFTS) return vae_set_error(what, "(2 max_pitch_shift + 1) * (2 max_time_shift + 1) must be <= 1023");
+    if (k < 1 || k > NR_MAX_K) return vae_set_error(what, "k must be in 1..32");
+    if (splits < 0 || splits > NR_MAX_SPLITS) return vae_set_error(what, "splits must be in 0..64");
+    if ((reinterpret_cast<uintptr_t>(queries) | reinterpret_cast<uintptr_t>(rolls)) & 3) return vae_set_error(what, "queries and rolls must be 4-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(index) | reinterpret_cast<uintptr_t>(exclude)) & 7) return vae_set_error(what, "index and exclude must be 8-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(distance) | reinterpret_cast<uintptr_t>(shift) | reinterpret_cast<uintptr_t>(intersection) |
+         reinterpret_cast<uintptr_t>(query_cells)) & 3)
+        return vae_set_error(what, "distance, shift, intersection and query_cells must be 4-byte aligned");
+    if (n_queries == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const int wd = w / 32, words = h * wd;
+    const bool large = words * 4 > NR_TILE_ROLL_BYTES;
+    const int qt = large ? NR_LARGE_TILE : NR_QUERY_TILE, ct = large ? NR_LARGE_TILE : NR_CAND_TILE;
+    const long qtiles = ((long)n_queries + qt - 1) / qt;
+    if (splits == 0) splits = (int)std::max<long>(1, std::min<long>({(1024 + qtiles - 1) / qtiles, (long)((n_rolls + ct - 1) / ct), (long)NR_MAX_SPLITS}));
+    if (qtiles * splits > INT32_MAX) return vae_set_error(what, "query tiles * splits must stay below 2^31");
+    // 0: no time shift, 16-byte LDS reads; 1: no time shift, dwords; 2: any window; 3: |dt| < 32 on rows of whole 16-byte chunks;
+    // 4: |dt| < 32 on rows of one chunk
+    const int mode = T == 0 ? ((wd % 4 == 0 || (P == 0 && words % 4 == 0)) ? 0 : 1) : ((wd % 4 == 0 && T < 32) ? (wd == 4 ? 4 : 3) : 2);
+    const size_t lds = (size_t)(qt + ct) * (((words + 7) & ~7) + 4) * sizeof(unsigned);
+    const size_t nlist = (size_t)n_queries * splits * k, key_bytes = (nlist * sizeof(nr_u64) + 255) / 256 * 256;
+    return with_stream_scratch(key_bytes + nlist * sizeof(unsigned), st, [&](char* base) -> int {
+        NrArgs a{reinterpret_cast<const unsigned*>(queries), n_queries, reinterpret_cast<const unsigned*>(rolls), (long)n_rolls, h, wd, P, T,
+                 reinterpret_cast<const long long*>(exclude), k, splits, reinterpret_cast<nr_u64*>(base), reinterpret_cast<unsigned*>(base + key_bytes),
+                 reinterpret_cast<long long*>(index), distance, shift, intersection, query_cells};
+        const dim3 grid((unsigned)(qtiles * splits));
+        if (pick_const<0, 1, 2, 3, 4>("nearest_rolls_kernel", mode, [&](auto M) {
+                if (large) return launch("nearest_rolls_kernel", nearest_rolls_kernel<NR_LARGE_TILE, 1, decltype(M)::value>, grid, dim3(64), lds, st, a);
+                return launch("nearest_rolls_kernel", nearest_rolls_kernel<4, 4, decltype(M)::value>, grid, dim3(256), lds, st, a); })) return -1;
+        return launch("nearest_merge_kernel", nearest_merge_kernel, dim3((unsigned)n_queries), dim3(64), 0, st, a);
     });
 }
 

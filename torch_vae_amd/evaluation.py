@@ -10,7 +10,7 @@ import math
 import torch
 
 from . import _lib
-from .types_helpers import LatentStatsOutput, ReconMetricsOutput
+from .types_helpers import LatentStatsOutput, NearestRolls, ReconMetricsOutput
 
 MAX_LATENT_DIM = 4096
 MAX_NOTE_THRESHOLDS = _lib.RECON_METRICS_MAX_THRESHOLDS
@@ -279,6 +279,132 @@ def note_event_metrics(pred, ref, *, onset_tolerance=1) -> dict:
     if isinstance(onset_tolerance, bool) or int(onset_tolerance) != onset_tolerance or onset_tolerance < 0:
         raise ValueError(f"onset_tolerance must be an integer >= 0, got {onset_tolerance}")
     return note_event_ratios(*_count_note_matches(_host_events(pred), _host_events(ref), int(onset_tolerance)))
+
+
+def _query_planes(queries, threshold):
+    """Tensor queries of nearest_rolls as contiguous uint8 planes [Q, h, w/8] on the GPU."""
+    if not isinstance(queries, torch.Tensor):
+        raise TypeError("queries must be a tensor or a PianorollDataset")
+    if queries.device.type != "cuda":
+        raise ValueError("queries must be on the GPU: the search runs on the HIP kernels only")
+    if queries.dtype == torch.float32:
+        from .generation import binarize_rolls
+        return binarize_rolls(queries.contiguous(), threshold)
+    if queries.dtype != torch.uint8:
+        raise TypeError(f"queries must be uint8 bit planes or float32 rolls, got {queries.dtype}")
+    if queries.dim() != 3:
+        raise ValueError(f"bit-plane queries must be [Q, h, w/8], got {tuple(queries.shape)}")
+    return queries.detach().contiguous()
+
+
+def nearest_rolls(queries, dataset, k=1, *, max_pitch_shift=0, max_time_shift=0, exclude=None, threshold=0.5) -> NearestRolls:
+    """The ``k`` rolls of ``dataset`` nearest to each query under transposition and time shift, on the device (include/vae_step.h:
+    vae_nearest_rolls has the definition).  ``queries``: uint8 bit planes [Q,h,w/8], float32 rolls [Q,h,w] or [Q,1,h,w] (cut at
+    ``threshold`` by ``generation.binarize_rolls``) on the GPU, or a ``PianorollDataset`` with "bits" storage.  ``dataset``: a
+    ``PianorollDataset`` with "bits" storage on the device, of the same height and width.  The distance of a pair is the smallest
+    Hamming distance over transpositions of up to ``max_pitch_shift`` rows and shifts of up to ``max_time_shift`` steps of the
+    dataset roll (zero-filled, as the training augmentation does it); neighbours ascend by (distance, index).  ``exclude``: None,
+    an int64 [Q] GPU tensor of dataset indices to leave out per query, or "self" (needs ``queries is dataset``): the near-duplicate
+    search of a dataset against itself.  ``k > len(dataset)`` leaves slots of index -1.  Returns device tensors (NearestRolls);
+    nothing is read back.  Repeated calls give the same bits."""
+    from .data import PianorollDataset
+    if not isinstance(dataset, PianorollDataset):
+        raise TypeError("dataset must be a PianorollDataset")
+    if dataset.storage != "bits":
+        raise ValueError(f"the dataset must have 'bits' storage, got {dataset.storage!r}")
+    if isinstance(k, bool) or int(k) != k or not 1 <= k <= _lib.NEAREST_MAX_K:
+        raise ValueError(f"k must be an integer in 1..{_lib.NEAREST_MAX_K}, got {k}")
+    for name, v in (("max_pitch_shift", max_pitch_shift), ("max_time_shift", max_time_shift)):
+        if isinstance(v, bool) or int(v) != v or v < 0:
+            raise ValueError(f"{name} must be an integer >= 0, got {v}")
+    if isinstance(exclude, str):
+        if exclude != "self":
+            raise ValueError(f"exclude must be None, 'self' or an int64 tensor, got {exclude!r}")
+        if queries is not dataset:
+            raise ValueError("exclude='self' needs the dataset itself as queries")
+    if isinstance(queries, PianorollDataset):
+        if queries.storage != "bits":
+            raise ValueError(f"a dataset used as queries must have 'bits' storage, got {queries.storage!r}")
+        planes = queries.data
+    else:
+        planes = _query_planes(queries, threshold)
+    rolls = dataset.data
+    Q, h, wb = (int(s) for s in planes.shape)
+    if (h, wb * 8) != (dataset.height, dataset.width):
+        raise ValueError(f"queries are {h}x{wb * 8}, the dataset's rolls {dataset.height}x{dataset.width}")
+    if dataset.pinned or not rolls.is_cuda:
+        raise ValueError("the dataset must be on the device, not in pinned host memory: the kernel reads every roll once per query "
+                         "tile, which the host link cannot feed")
+    if not planes.is_cuda:
+        raise ValueError("a dataset used as queries must be on the device, not in pinned host memory")
+    if planes.device != rolls.device:
+        raise ValueError(f"queries are on {planes.device}, the dataset on {rolls.device}")
+    dev = rolls.device
+    if isinstance(exclude, str):
+        exclude = torch.arange(Q, dtype=torch.int64, device=dev)
+    elif exclude is not None:
+        if not isinstance(exclude, torch.Tensor) or exclude.dtype != torch.int64 or tuple(exclude.shape) != (Q,) or exclude.device != dev:
+            raise ValueError(f"exclude must be an int64 [{Q}] tensor on {dev}")
+        exclude = exclude.contiguous()
+    k = int(k)
+    index = torch.full((Q, k), -1, dtype=torch.int64, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    distance, shift = torch.full((Q, k), -1, **i32), torch.zeros(Q, k, 2, **i32)
+    inter, cells = torch.zeros(Q, k, **i32), torch.zeros(Q, **i32)
+    if Q:      # (an empty tensor has no address to hand over)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().vae_nearest_rolls(
+                planes.data_ptr(), Q, rolls.data_ptr(), len(dataset), h, wb * 8, int(max_pitch_shift), int(max_time_shift),
+                _lib.ptr(exclude), k, 0, index.data_ptr(), distance.data_ptr(), shift.data_ptr(), inter.data_ptr(), cells.data_ptr(),
+                torch.cuda.current_stream(dev).cuda_stream), "vae_nearest_rolls")
+    return _nearest_result(index, distance, shift, inter, cells)
+
+
+def _nearest_result(index, distance, shift, intersection, query_cells) -> NearestRolls:
+    """The derived fields: the shifted neighbour's cells d + 2 inter - |q|, and the Jaccard index inter / (d + inter) - the union
+    is the differing cells plus the common ones - as float64, 1.0 where both rolls are empty, nan in empty slots."""
+    found = index >= 0
+    ncells = torch.where(found, distance + 2 * intersection - query_cells[:, None], torch.zeros_like(distance))
+    union = (distance + intersection).double()
+    jac = torch.where(union > 0, intersection.double() / union.clamp_min(1.0), torch.ones_like(union))
+    jac = torch.where(found, jac, torch.full_like(jac, float("nan")))
+    return NearestRolls(index=index, distance=distance, shift=shift, intersection=intersection, query_cells=query_cells,
+                        neighbour_cells=ncells, jaccard=jac)
+
+
+def novelty_summary(result, copy_jaccard=0.9) -> dict:
+    """What a nearest_rolls result says about novelty, with one read-back (CPU tensors work too).  Over the queries that have a
+    nearest neighbour: ``count``; ``copies``, the share whose nearest neighbour has ``jaccard >= copy_jaccard``;
+    ``shifted_copies``, the share that are copies found at a non-zero shift; ``median_jaccard`` and ``mean_distance`` of the nearest
+    neighbour.  ``without_neighbour`` counts the others (every roll excluded, or none there).  With no query left the shares and
+    means are 0.0."""
+    cj = float(copy_jaccard)
+    if not 0.0 <= cj <= 1.0:
+        raise ValueError(f"copy_jaccard must be in [0, 1], got {copy_jaccard!r}")
+    idx, jac = result["index"][:, 0], result["jaccard"][:, 0]
+    host = torch.stack([idx.double(), jac.double(), result["distance"][:, 0].double(),
+                        (result["shift"][:, 0] != 0).any(dim=-1).double()]).cpu()
+    found = host[0] >= 0
+    n = int(found.sum())
+    out = {"count": n, "without_neighbour": int(idx.numel()) - n, "copies": 0.0, "shifted_copies": 0.0, "median_jaccard": 0.0,
+           "mean_distance": 0.0}
+    if n:
+        j, d, moved = host[1][found], host[2][found], host[3][found] > 0
+        copy = j >= cj
+        out.update(copies=int(copy.sum()) / n, shifted_copies=int((copy & moved).sum()) / n,
+                   median_jaccard=float(j.sort().values[(n - 1) // 2]) if n % 2 else float(j.sort().values[n // 2 - 1:n // 2 + 1].mean()),
+                   mean_distance=float(d.mean()))
+    return out
+
+
+def sample_novelty(model, dataset, num_samples, *, temperature=1.0, seed=None, k=1, max_pitch_shift=0, max_time_shift=0,
+                   copy_jaccard=0.9, **extract_kwargs):
+    """Is what the model generates new?  ``model.sample_notes(num_samples, temperature=..., seed=..., cleaned=True,
+    **extract_kwargs)``, then nearest_rolls of the cleaned planes in ``dataset`` under the shift window.  Returns
+    ``(novelty_summary, NearestRolls, NoteEvents)``."""
+    notes = model.sample_notes(int(num_samples), temperature=temperature, seed=seed, cleaned=True, **extract_kwargs)
+    near = nearest_rolls(notes["cleaned"], dataset, k, max_pitch_shift=max_pitch_shift, max_time_shift=max_time_shift)
+    return novelty_summary(near, copy_jaccard), near, notes
 
 
 def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nll_samples=0, latent_rolls=0, note_thresholds=None,

@@ -63,6 +63,16 @@ class ReconMetricsOutput(TypedDict):
     roll_fp: Tensor           # [N, T] int64
 
 
+class NearestRolls(TypedDict):
+    index: Tensor             # [Q, k] int64: the neighbours ascending by (distance, index); -1 where none is left
+    distance: Tensor          # [Q, k] int32: min over the shift window of popcount(q XOR shifted roll); -1 in empty slots
+    shift: Tensor             # [Q, k, 2] int32: (dy, dt) of the lowest-ranked shift that reaches the distance
+    intersection: Tensor      # [Q, k] int32: popcount(q AND shifted roll) at that shift
+    query_cells: Tensor       # [Q] int32: popcount(q)
+    neighbour_cells: Tensor   # [Q, k] int32: cells of the shifted neighbour, d + 2 * intersection - query_cells (0 in empty slots)
+    jaccard: Tensor           # [Q, k] float64: intersection / (d + intersection); 1.0 where both are empty, nan in empty slots
+
+
 class NoteEvents(TypedDict):
     events: Tensor            # [N, 4] int32: (roll, pitch, onset, duration), ascending by (roll, pitch, onset)
     peaks: Tensor             # [N] float32: the largest input value over the note's cells (NaNs skipped), exact
