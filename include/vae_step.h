@@ -19,6 +19,13 @@
  * 0 on success or a negative code, with the message in vae_last_error().  A context is
  * not re-entrant; use one per process / GPU.
  *
+ * Work space "from the stream-ordered allocator": requests of up to 64 MiB share one block per
+ * device and stream, which the library keeps for the life of the process and grows on demand
+ * (calls on a stream run in stream order).  After the first call at a size such an entry point
+ * allocates nothing and never makes the host wait.  Larger requests, a stream that is being
+ * captured into a graph, and hipStreamPerThread are allocated and released on the stream per
+ * call; outside a capture the host may then wait for an earlier release.
+ *
  * A context holds at most ONE forward (vae_forward, a training step, vae_encode or vae_decode):
  * vae_loss*, vae_backward* and the read-back calls act on it, and the next forward replaces it.
  * A call refused for its arguments (null pointer, batch above max_batch) touches nothing: the

@@ -9,6 +9,9 @@
 #include <string>
 #include <vector>
 #include <algorithm>
+#include <map>
+#include <mutex>
+#include <utility>
 #include <type_traits>
 
 #include "../../include/vae_step.h"
@@ -48,16 +51,38 @@ static int pick_const(const char* what, int v, F&& f) {
 }
 template <typename F> static int pick_bool(bool v, F&& f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
 
-// Work space of `bytes` from the stream-ordered allocator for what body(char* base) enqueues on `st`; freed on the stream behind
-// it whatever body returned.  body's error wins over a failed free; a failed allocation returns before body runs.
+// Work space of `bytes` from the stream-ordered allocator for what body(char* base) enqueues on `st`.  Requests of up to
+// kScratchKeep bytes share ONE block per (device, stream) in the whole library (the table lives in vae_util.hip), kept between calls
+// and grown on demand: calls on a stream run in stream order, so each may overwrite what the one before it left.  (An allocation and
+// a release per call made the host WAIT: a hipMallocAsync that finds the block of a hipFreeAsync still pending on the stream blocks
+// until the stream has passed that release - the second of two calls in a row waited for everything enqueued in front of the first.)
+// A block that has become too small is released on the stream behind its last user, after its successor has been allocated; a
+// block is never released otherwise: every stream handle such a call has seen keeps up to kScratchKeep bytes for the life of the
+// process.  Larger requests, a stream that is being captured, and hipStreamPerThread (one handle value, another stream in every
+// thread) are allocated and released per call as before.  The mutex is held while body enqueues: two threads on one stream must not
+// interleave there.  body's error wins over a failed free; a failed allocation returns before body runs.
+static const size_t kScratchKeep = (size_t)64 << 20;
+std::mutex& stream_scratch_mutex();
+// the kept block of (current device, st), at least `bytes` large; the caller holds stream_scratch_mutex()
+int kept_stream_scratch(size_t bytes, hipStream_t st, char** base);
 template <typename F> static int with_stream_scratch(size_t bytes, hipStream_t st, F&& body) {
-    void* ws = nullptr;
-    HIP_CHECK_RET(hipMallocAsync(&ws, bytes, st));
-    const int rc = body(static_cast<char*>(ws));
-    const hipError_t fe = hipFreeAsync(ws, st);
-    if (rc) return rc;
-    if (fe != hipSuccess) return vae_set_error("hipFreeAsync", hipGetErrorString(fe));
-    return 0;
+    // (a stream that is being captured into a graph takes the per-call form too: the allocation and the release become nodes of
+    //  that graph, and a block allocated inside a capture must not be handed to calls outside it)
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &capturing) != hipSuccess) { (void)hipGetLastError(); capturing = hipStreamCaptureStatusNone; }
+    if (bytes > kScratchKeep || capturing != hipStreamCaptureStatusNone || st == hipStreamPerThread) {
+        void* ws = nullptr;
+        HIP_CHECK_RET(hipMallocAsync(&ws, bytes, st));
+        const int rc = body(static_cast<char*>(ws));
+        const hipError_t fe = hipFreeAsync(ws, st);
+        if (rc) return rc;
+        if (fe != hipSuccess) return vae_set_error("hipFreeAsync", hipGetErrorString(fe));
+        return 0;
+    }
+    std::lock_guard<std::mutex> lock(stream_scratch_mutex());
+    char* base = nullptr;
+    if (kept_stream_scratch(bytes, st, &base)) return -1;
+    return body(base);
 }
 
 static const int kBnC[8] = {32, 64, 128, 256, 128, 64, 32, 32};

@@ -1,13 +1,32 @@
 // Context-free utilities of the C ABI (include/vae_step.h): data synthesis and stimulus expansion, the ds_read_b64_tr_b16 self-test,
 // latent diagnostics, reconstruction metrics, the resident-pianoroll gather with its augmentation, the note-event extraction and
 // the nearest-roll search.
-// Nothing here touches a context or shares a helper with vae_api.hip.
+// Nothing here touches a context; the one thing shared with vae_api.hip is the table of kept stream work space (below).
 #include "vae_ctx.h"
 #include "latent_stats.cuh"
 #include "recon_metrics.cuh"
 #include "augment.cuh"
 #include "note_events.cuh"
 #include "nearest_rolls.cuh"
+
+// The kept work space of with_stream_scratch (vae_ctx.h): one table and one mutex for the whole library.
+struct StreamScratch { void* p = nullptr; size_t cap = 0; };
+std::mutex& stream_scratch_mutex() { static std::mutex mu; return mu; }
+int kept_stream_scratch(size_t bytes, hipStream_t st, char** base) {
+    static std::map<std::pair<int, hipStream_t>, StreamScratch> kept;
+    int dev = 0;
+    HIP_CHECK_RET(hipGetDevice(&dev));
+    StreamScratch& s = kept[std::make_pair(dev, st)];
+    if (!s.p || s.cap < bytes) {
+        const size_t cap = std::max<size_t>((bytes + 4095) / 4096 * 4096, 4096);
+        void* ws = nullptr;
+        HIP_CHECK_RET(hipMallocAsync(&ws, cap, st));
+        if (s.p) (void)hipFreeAsync(s.p, st);
+        s.p = ws; s.cap = cap;
+    }
+    *base = static_cast<char*>(s.p);
+    return 0;
+}
 
 // data_generators.py:45-77 restated with the counter generator (stream 777); one workgroup per image
 __global__ void synth_pianoroll_kernel(float* x, int H, unsigned long long seed, int max_lines) {

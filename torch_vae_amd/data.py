@@ -260,7 +260,10 @@ class DevicePianorollLoader:
         ds = self.dataset
         idx = epoch_indices(len(ds), seed=self.seed, epoch=self.epoch, shuffle=self.shuffle, rank=self.rank, world=self.world)
         dev = ds.data.device if ds.data.is_cuda else torch.device("cuda", torch.cuda.current_device())
-        index = idx.to(dev)      # the epoch's one host-to-device copy
+        # the epoch's one host-to-device copy: from pinned memory and asynchronous, so that starting an epoch does not make the host
+        # wait for the stream (a blocking copy of a pageable tensor does); the loader keeps the host tensor until the next epoch
+        self._index_host = idx.pin_memory()
+        index = self._index_host.to(dev, non_blocking=True)
         if self._labels is None or self._labels.device != dev:
             self._labels = torch.zeros(self.batch_size, dtype=torch.long, device=dev)
         for k in range(len(self)):
