@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI library (include/vae_step.h).
+"""ctypes binding of the C-ABI library (include/vae_step.h, and include/vae_mixture.h for the latent mixture).
 
 The product path has no CPU fallback: if the HIP library is missing this module
 raises at import of the first symbol, loudly.
@@ -40,6 +40,10 @@ GATHER_THREADS, GATHER_MAX_BLOCKS, GATHER_CELLS_PER_LANE, GATHER_MAX_ROW_LANES =
 NEAREST_QUERY_TILE, NEAREST_CAND_TILE, NEAREST_TILE_ROLL_BYTES, NEAREST_LARGE_TILE = 16, 16, 4608, 8
 NEAREST_MAX_ROLL_BYTES, NEAREST_MAX_SHIFTS, NEAREST_MAX_K, NEAREST_MAX_SPLITS = 8192, 1023, 32, 64
 GRAD_CLIP_SCRATCH_BYTES = 8192  # include/vae_step.h: VAE_GRAD_CLIP_SCRATCH_BYTES
+# include/vae_mixture.h: covariance kinds, the limits on (components, latent_dim) and the sampler's two counter-generator streams
+MIXTURE_FULL, MIXTURE_DIAG = 0, 1
+MIXTURE_MAX_COMPONENTS, MIXTURE_MAX_DIM_FULL, MIXTURE_MAX_DIM_DIAG = 64, 128, 4096
+MIXTURE_STREAM_U, MIXTURE_STREAM_EPS = 811, 812
 
 PARAM_NAMES = (
     [f"encoder.{i}.{j}" for i in range(4) for j in ("0.weight", "0.bias", "1.weight", "1.bias")]
@@ -136,6 +140,12 @@ def lib():
     _sig(L.vae_selftest_tr16, i32, [p])
     _sig(L.vae_set_option, i32, [p, C.c_char_p, i32])
     _sig(L.vae_option_info, i32, [i32, C.POINTER(C.c_char_p), C.POINTER(C.c_int)])
+    # include/vae_mixture.h
+    _sig(L.vae_mixture_factor, i32, [p, i32, i32, i32, p, p, p, p, p, p])
+    _sig(L.vae_mixture_log_prob, i32, [p, i64, i32, i32, i32, p, p, p, p, p, p, p, p])
+    _sig(L.vae_mixture_mstep, i32, [p, p, i64, i32, i32, i32, f64, p, p, p, p])
+    _sig(L.vae_mixture_sample, i32, [i64, i32, i32, i32, p, p, p, f64, u64, p, p, p, p, p])
+    _sig(L.vae_mixture_em, i32, [p, i64, i32, i32, i32, i32, f64, p, p, p, p, p, p, p, p, p, p])
     _lib = L
     return L
 
@@ -152,6 +162,10 @@ EXPORTS = [
     "vae_selftest_tr16", "vae_set_option", "vae_option_info", "vae_gather_rolls", "vae_augment_params",
     "vae_extract_notes", "vae_nearest_rolls",
 ]
+
+
+# include/vae_mixture.h (a header of its own: EXPORTS above is exactly what include/vae_step.h declares)
+MIXTURE_EXPORTS = ["vae_mixture_factor", "vae_mixture_log_prob", "vae_mixture_mstep", "vae_mixture_sample", "vae_mixture_em"]
 
 
 def check(rc: int, what: str = ""):

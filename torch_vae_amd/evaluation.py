@@ -398,10 +398,13 @@ def novelty_summary(result, copy_jaccard=0.9) -> dict:
 
 
 def sample_novelty(model, dataset, num_samples, *, temperature=1.0, seed=None, k=1, max_pitch_shift=0, max_time_shift=0,
-                   copy_jaccard=0.9, **extract_kwargs):
+                   copy_jaccard=0.9, prior=None, **extract_kwargs):
     """Is what the model generates new?  ``model.sample_notes(num_samples, temperature=..., seed=..., cleaned=True,
     **extract_kwargs)``, then nearest_rolls of the cleaned planes in ``dataset`` under the shift window.  Returns
-    ``(novelty_summary, NearestRolls, NoteEvents)``."""
+    ``(novelty_summary, NearestRolls, NoteEvents)``.  ``prior``: a ``mixture.LatentMixture`` to draw the latents from instead of
+    N(0, I) (``sample_notes(prior=...)``)."""
+    if prior is not None:
+        extract_kwargs = dict(extract_kwargs, prior=prior)
     notes = model.sample_notes(int(num_samples), temperature=temperature, seed=seed, cleaned=True, **extract_kwargs)
     near = nearest_rolls(notes["cleaned"], dataset, k, max_pitch_shift=max_pitch_shift, max_time_shift=max_time_shift)
     return novelty_summary(near, copy_jaccard), near, notes

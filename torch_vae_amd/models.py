@@ -909,28 +909,40 @@ class VanillaVAE(nn.Module):
             _lib.check(_lib.lib().vae_last_total_correlation(self._ctx.handle, out.data_ptr(), self._stream()), "vae_last_total_correlation")
         return out
 
-    def sample(self, num_samples: int, current_device: int, **kwargs) -> Tensor:
-        """models.py:250-263: z ~ N(0, I) on the host generator, moved to the device, decoded."""
+    def sample(self, num_samples: int, current_device: int, *, prior=None, temperature: float = 1.0, seed: int = 0, **kwargs) -> Tensor:
+        """models.py:250-263: z ~ N(0, I) on the host generator, moved to the device, decoded.  With ``prior`` (a
+        ``mixture.LatentMixture`` on the model's device) z = prior.sample(num_samples, temperature=..., seed=...) instead;
+        ``temperature`` and ``seed`` are read only then."""
+        if prior is not None:
+            z = prior.sample(int(num_samples), temperature=temperature, seed=seed)
+            with torch.no_grad():
+                return self.decode(z)
         z = torch.randn(num_samples, self.latent_dim)
         z = z.to(current_device)
         with torch.no_grad():
             return self.decode(z)
 
     def sample_notes(self, num_samples: int, *, temperature: float = 1.0, seed: int | None = None, return_rolls: bool = False,
-                     **extract_kwargs):
+                     prior=None, **extract_kwargs):
         """Generated music as notes: z = temperature * N(0, I) from a ``torch.Generator`` on the model's device (seeded with
         ``seed`` when given), decoded with running statistics (eval mode, whatever mode the model is in; it is left in that
         mode and nothing of it changes), then ``generation.extract_notes(rolls, **extract_kwargs)``.  Returns the NoteEvents,
-        with the decoded ``rolls`` [num_samples,1,H,W] added under that key when ``return_rolls``."""
+        with the decoded ``rolls`` [num_samples,1,H,W] added under that key when ``return_rolls``.  With ``prior`` (a
+        ``mixture.LatentMixture`` fitted to the encodings) z = prior.sample(num_samples, temperature=..., seed=...) instead
+        (``seed`` None: one drawn from torch's host generator)."""
         from .generation import extract_notes
         self._require_device()
         dev = self._flat.device
-        g = torch.Generator(device=dev)
-        if seed is None:
-            g.seed()
+        if prior is not None:
+            z = prior.sample(int(num_samples), temperature=temperature,
+                             seed=int(torch.randint(0, 2 ** 62, (1,))) if seed is None else int(seed))
         else:
-            g.manual_seed(int(seed))
-        z = float(temperature) * torch.randn(int(num_samples), self.latent_dim, generator=g, device=dev, dtype=torch.float32)
+            g = torch.Generator(device=dev)
+            if seed is None:
+                g.seed()
+            else:
+                g.manual_seed(int(seed))
+            z = float(temperature) * torch.randn(int(num_samples), self.latent_dim, generator=g, device=dev, dtype=torch.float32)
         with torch.no_grad():
             rolls = self._run_decode(z, train=False)
         out = extract_notes(rolls, **extract_kwargs)
