@@ -1,4 +1,5 @@
-"""ctypes binding of the C-ABI library (include/vae_step.h, and include/vae_mixture.h for the latent mixture).
+"""ctypes binding of the C-ABI library (include/vae_step.h, include/vae_mixture.h for the latent mixture and include/vae_music.h
+for the musical statistics).
 
 The product path has no CPU fallback: if the HIP library is missing this module
 raises at import of the first symbol, loudly.
@@ -44,6 +45,8 @@ GRAD_CLIP_SCRATCH_BYTES = 8192  # include/vae_step.h: VAE_GRAD_CLIP_SCRATCH_BYTE
 MIXTURE_FULL, MIXTURE_DIAG = 0, 1
 MIXTURE_MAX_COMPONENTS, MIXTURE_MAX_DIM_FULL, MIXTURE_MAX_DIM_DIAG = 64, 128, 4096
 MIXTURE_STREAM_U, MIXTURE_STREAM_EPS = 811, 812
+# include/vae_music.h: the width of a feature row; the limits of vae_music_roll_stats
+MUSIC_FEATURES, MUSIC_MAX_ROLL_BYTES, MUSIC_MAX_PITCH_OFFSET = 76, 8192, 1 << 20
 
 PARAM_NAMES = (
     [f"encoder.{i}.{j}" for i in range(4) for j in ("0.weight", "0.bias", "1.weight", "1.bias")]
@@ -146,6 +149,8 @@ def lib():
     _sig(L.vae_mixture_mstep, i32, [p, p, i64, i32, i32, i32, f64, p, p, p, p])
     _sig(L.vae_mixture_sample, i32, [i64, i32, i32, i32, p, p, p, f64, u64, p, p, p, p, p])
     _sig(L.vae_mixture_em, i32, [p, i64, i32, i32, i32, i32, f64, p, p, p, p, p, p, p, p, p, p])
+    # include/vae_music.h
+    _sig(L.vae_music_roll_stats, i32, [p, i64, i32, i32, i32, p, p, i32, p])
     _lib = L
     return L
 
@@ -166,6 +171,9 @@ EXPORTS = [
 
 # include/vae_mixture.h (a header of its own: EXPORTS above is exactly what include/vae_step.h declares)
 MIXTURE_EXPORTS = ["vae_mixture_factor", "vae_mixture_log_prob", "vae_mixture_mstep", "vae_mixture_sample", "vae_mixture_em"]
+
+# include/vae_music.h (its own header too)
+MUSIC_EXPORTS = ["vae_music_roll_stats"]
 
 
 def check(rc: int, what: str = ""):

@@ -10,7 +10,7 @@ import math
 import torch
 
 from . import _lib
-from .types_helpers import LatentStatsOutput, NearestRolls, ReconMetricsOutput
+from .types_helpers import LatentStatsOutput, MusicStats, NearestRolls, ReconMetricsOutput
 
 MAX_LATENT_DIM = 4096
 MAX_NOTE_THRESHOLDS = _lib.RECON_METRICS_MAX_THRESHOLDS
@@ -410,8 +410,282 @@ def sample_novelty(model, dataset, num_samples, *, temperature=1.0, seed=None, k
     return novelty_summary(near, copy_jaccard), near, notes
 
 
+# ---- musical statistics of sets of rolls (include/vae_music.h) ---------------------------------------------------------------------
+MUSIC_FEATURES = _lib.MUSIC_FEATURES
+MUSIC_COLUMNS = {
+    "rolls": slice(0, 1), "nonempty": slice(1, 2), "cells": slice(2, 3), "notes": slice(3, 4), "used_pitches": slice(4, 5),
+    "lowest": slice(5, 6), "highest": slice(6, 7), "sounding_steps": slice(7, 8), "onset_steps": slice(8, 9),
+    "max_polyphony": slice(9, 10), "pc_cells": slice(10, 22), "pc_notes": slice(22, 34), "duration": slice(34, 46),
+    "polyphony": slice(46, 62), "ioi": slice(62, 74),
+}
+# the normalised distributions of music_summary / compare_music and the columns they are made of
+MUSIC_DISTRIBUTIONS = {"pitch_class": "pc_cells", "pitch_class_onsets": "pc_notes", "duration": "duration", "polyphony": "polyphony",
+                       "ioi": "ioi"}
+MUSIC_SCALARS = ("notes", "cells", "used_pitches", "pitch_range", "max_polyphony")     # per-roll numbers compare_music holds against each other
+MAJOR_SCALE = (0, 2, 4, 5, 7, 9, 11)
+_NAN = float("nan")
+
+
+def _music_pitch_offset(pitch_offset):
+    if isinstance(pitch_offset, bool) or int(pitch_offset) != pitch_offset or not 0 <= pitch_offset <= _lib.MUSIC_MAX_PITCH_OFFSET:
+        raise ValueError(f"pitch_offset must be an integer in 0..{_lib.MUSIC_MAX_PITCH_OFFSET}, got {pitch_offset}")
+    return int(pitch_offset)
+
+
+def _music_checked_shape(h, w):
+    if h < 1 or w < 32 or w % 32:
+        raise ValueError(f"need at least one pitch row and a width (time steps) that is a positive multiple of 32, got {h}x{w}")
+    if h * (w // 8) > _lib.MUSIC_MAX_ROLL_BYTES:
+        raise ValueError(f"a roll of {h}x{w} cells takes {h * (w // 8)} bytes as bit planes, above the {_lib.MUSIC_MAX_ROLL_BYTES} the kernel holds")
+
+
+def _music_planes(rolls, threshold):
+    """The rolls of music_statistics as contiguous uint8 planes [n, h, w/8] on the GPU, with (n, h, w)."""
+    from .data import PianorollDataset
+    if isinstance(rolls, PianorollDataset):
+        if rolls.storage != "bits":
+            raise ValueError(f"a dataset must have 'bits' storage, got {rolls.storage!r}")
+        if rolls.pinned or not rolls.data.is_cuda:
+            raise ValueError("the dataset must be on the device, not in pinned host memory")
+        planes = rolls.data
+    elif not isinstance(rolls, torch.Tensor):
+        raise TypeError("rolls must be a tensor or a PianorollDataset")
+    elif rolls.dtype == torch.float32:
+        if rolls.dim() not in (3, 4) or (rolls.dim() == 4 and rolls.shape[1] != 1):
+            raise ValueError(f"float32 rolls must be [n, h, w] or [n, 1, h, w], got {tuple(rolls.shape)}")
+        h, w = int(rolls.shape[-2]), int(rolls.shape[-1])
+        _music_checked_shape(h, w)
+        if rolls.device.type != "cuda":
+            raise ValueError("rolls must be on the GPU: the statistics run on the HIP kernels only")
+        from .generation import binarize_rolls
+        planes = binarize_rolls(rolls.detach().contiguous(), threshold)
+    elif rolls.dtype != torch.uint8:
+        raise TypeError(f"rolls must be uint8 bit planes or float32 rolls, got {rolls.dtype}")
+    elif rolls.dim() != 3:
+        raise ValueError(f"bit-plane rolls must be [n, h, w/8], got {tuple(rolls.shape)}")
+    else:
+        planes = rolls.detach().contiguous()
+    n, h, wb = (int(v) for v in planes.shape)
+    _music_checked_shape(h, wb * 8)
+    if planes.device.type != "cuda":
+        raise ValueError("rolls must be on the GPU: the statistics run on the HIP kernels only")
+    return planes, n, h, wb * 8
+
+
+def _music_empty_totals(dev):
+    """zeros, lowest -1, highest -1 (built on the device: a copy from host memory would wait for the stream)"""
+    empty = torch.zeros(MUSIC_FEATURES, dtype=torch.int64, device=dev)
+    empty[5:7] = -1
+    return empty
+
+
+def _music_call(planes, n, h, w, pitch_offset, features, totals, accumulate):
+    dev = planes.device
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().vae_music_roll_stats(planes.data_ptr(), n, h, w, pitch_offset, features.data_ptr(), totals.data_ptr(),
+                                                   int(accumulate), torch.cuda.current_stream(dev).cuda_stream), "vae_music_roll_stats")
+
+
+def music_statistics(rolls, *, pitch_offset=0, threshold=0.5) -> MusicStats:
+    """What ``rolls`` are as music, counted on the device in one HIP pass over bit planes (include/vae_music.h: vae_music_roll_stats
+    has the table of the 76 columns).  ``rolls``: uint8 bit planes [n,h,w/8] on the GPU, float32 rolls [n,h,w] or [n,1,h,w] (cut at
+    ``threshold`` by ``generation.binarize_rolls``), or a ``PianorollDataset`` with "bits" storage on the device, whose planes are
+    used as they are.  A note is a maximal run of set cells along time in one pitch row; row p has pitch class
+    ``(p + pitch_offset) mod 12``.  w must be a multiple of 32 and a roll at most 8192 bytes of planes (256x256 fits).  Returns
+    device tensors - ``features`` int32 [n,76], ``totals`` int64 [76] - with ``columns`` (name -> slice of the 76, so nobody
+    indexes by number), ``height``, ``width`` and ``pitch_offset``; nothing is read back.  All counts are exact and repeat bit for
+    bit.  ``music_summary`` and ``compare_music`` turn them into numbers."""
+    off = _music_pitch_offset(pitch_offset)
+    planes, n, h, w = _music_planes(rolls, threshold)
+    dev = planes.device
+    features = torch.empty(n, MUSIC_FEATURES, dtype=torch.int32, device=dev)
+    if n:      # (an empty tensor has no address to hand over)
+        totals = torch.empty(MUSIC_FEATURES, dtype=torch.int64, device=dev)
+        _music_call(planes, n, h, w, off, features, totals, 0)
+    else:
+        totals = _music_empty_totals(dev)
+    return MusicStats(features=features, totals=totals, columns=dict(MUSIC_COLUMNS), height=h, width=w, pitch_offset=off)
+
+
+class MusicStatsAccumulator:
+    """music_statistics over a set that arrives in batches: update() makes one library call that adds the batch to totals the
+    accumulator owns (``accumulate=1``) and keeps the batch's per-roll table on the device; compute() returns the MusicStats of
+    everything seen.  Nothing is read back.  Every batch must have the shape of the first."""
+
+    def __init__(self, pitch_offset=0, threshold=0.5):
+        self.pitch_offset, self.threshold = _music_pitch_offset(pitch_offset), threshold
+        self._shape, self._totals, self._features = None, None, []
+
+    def update(self, rolls):
+        planes, n, h, w = _music_planes(rolls, self.threshold)
+        if self._shape is None:
+            self._shape, self._totals = (h, w), _music_empty_totals(planes.device)
+        elif self._shape != (h, w):
+            raise ValueError(f"the accumulator holds {self._shape[0]}x{self._shape[1]} rolls, this batch is {h}x{w}")
+        elif planes.device != self._totals.device:
+            raise ValueError(f"the accumulator lives on {self._totals.device}, the rolls on {planes.device}")
+        if not n:
+            return
+        features = torch.empty(n, MUSIC_FEATURES, dtype=torch.int32, device=planes.device)
+        _music_call(planes, n, h, w, self.pitch_offset, features, self._totals, 1)
+        self._features.append(features)
+
+    def compute(self) -> MusicStats:
+        if self._shape is None:
+            raise RuntimeError("nothing to compute: update() has not been called")
+        dev = self._totals.device
+        features = torch.cat(self._features) if self._features else torch.empty(0, MUSIC_FEATURES, dtype=torch.int32, device=dev)
+        self._features = [features] if self._features else []
+        return MusicStats(features=features, totals=self._totals, columns=dict(MUSIC_COLUMNS), height=self._shape[0],
+                          width=self._shape[1], pitch_offset=self.pitch_offset)
+
+
+def _ratio(a, b):
+    return a / b if b else _NAN
+
+
+def _normalised(counts):
+    total = sum(counts)
+    return [_ratio(c, total) for c in counts]
+
+
+def _scale_consistency(pc_cells):
+    """(the largest share of cells inside a major scale over its 12 roots, the lowest root that reaches it); (nan, -1) without cells"""
+    cells = sum(pc_cells)
+    if not cells:
+        return _NAN, -1
+    best, key = -1.0, -1
+    for root in range(12):
+        share = sum(pc_cells[(root + s) % 12] for s in MAJOR_SCALE) / cells
+        if share > best:
+            best, key = share, root
+    return best, key
+
+
+def _pitch_range_per_roll(features):
+    """highest - lowest + 1 per roll, 0 for an empty one (int64 [n], on the features' device)"""
+    f = features.to(torch.int64)
+    return (f[:, 6] - f[:, 5] + 1) * f[:, 1]
+
+
+def music_summary(stats) -> dict:
+    """A MusicStats as numbers, with one read-back and float64 arithmetic on the host: ``rolls``, ``empty_roll_rate``,
+    ``notes_per_roll``, ``note_density`` (cells / (rolls h w)), ``mean_duration`` (cells / notes, in steps), ``mean_polyphony``
+    (cells / sounding steps), ``empty_step_rate`` (the share of time steps with no cell), ``used_pitches`` and ``pitch_range``
+    (highest - lowest + 1), both means over the non-empty rolls; the normalised distributions ``pitch_class`` (of cells),
+    ``pitch_class_onsets`` (of notes), ``duration`` and ``ioi`` (12 buckets, bucket b holding lengths / gaps in [2^b, 2^(b+1)), the
+    last everything from 2048) and ``polyphony`` (steps with k = 0..14 cells, the last k >= 15) as lists; ``pitch_class_entropy``
+    in bits; ``scale_consistency``, the largest share of cells whose pitch class lies in a major scale over the 12 roots, and
+    ``key``, the lowest root that reaches it (-1 without cells).  A ratio with a zero denominator is nan."""
+    totals = stats["totals"]
+    host = torch.cat([totals.reshape(-1), _pitch_range_per_roll(stats["features"]).sum().reshape(1)]).cpu().tolist()
+    t, range_sum = host[:MUSIC_FEATURES], host[MUSIC_FEATURES]
+    col = lambda name: t[MUSIC_COLUMNS[name]]
+    rolls, nonempty, cells, notes = t[0], t[1], t[2], t[3]
+    poly = col("polyphony")
+    out = {"rolls": rolls, "empty_roll_rate": _ratio(rolls - nonempty, rolls), "notes_per_roll": _ratio(notes, rolls),
+           "note_density": _ratio(cells, rolls * stats["height"] * stats["width"]), "mean_duration": _ratio(cells, notes),
+           "mean_polyphony": _ratio(cells, t[7]), "empty_step_rate": _ratio(poly[0], sum(poly)),
+           "used_pitches": _ratio(t[4], nonempty), "pitch_range": _ratio(range_sum, nonempty)}
+    for name, source in MUSIC_DISTRIBUTIONS.items():
+        out[name] = _normalised(col(source))
+    p = out["pitch_class"]
+    out["pitch_class_entropy"] = -sum(v * math.log2(v) for v in p if v > 0) if cells else _NAN
+    out["scale_consistency"], out["key"] = _scale_consistency(col("pc_cells"))
+    return out
+
+
+def _js_and_overlap(a, b):
+    """(Jensen-Shannon divergence in bits, sum of min(p, q)) of two lists of counts; (nan, nan) if either is empty"""
+    sa, sb = sum(a), sum(b)
+    if not sa or not sb:
+        return _NAN, _NAN
+    js = overlap = 0.0
+    for ca, cb in zip(a, b):
+        p, q = ca / sa, cb / sb
+        m = 0.5 * (p + q)
+        # (each bin's share of the divergence is >= 0: nothing cancels between bins)
+        js += (0.5 * p * math.log2(p / m) if p > 0 else 0.0) + (0.5 * q * math.log2(q / m) if q > 0 else 0.0)
+        overlap += min(p, q)
+    return js, overlap
+
+
+def _wasserstein1(x, y):
+    """sum over integers v of |F_x(v) - F_y(v)| for two host int64 vectors of non-negative values; nan if either is empty"""
+    if not x.numel() or not y.numel():
+        return _NAN
+    size = int(max(x.max(), y.max())) + 1
+    fx = torch.bincount(x, minlength=size).cumsum(0).double() / x.numel()
+    fy = torch.bincount(y, minlength=size).cumsum(0).double() / y.numel()
+    return float((fx - fy).abs().sum())
+
+
+def _music_host(stats):
+    """One read-back of what compare_music needs: (totals as a list, the per-roll scalars as a host int64 [5, n] tensor)"""
+    f = stats["features"].to(torch.int64)
+    per_roll = torch.stack([f[:, 3], f[:, 2], f[:, 4], _pitch_range_per_roll(stats["features"]), f[:, 9]]).reshape(-1)
+    host = torch.cat([stats["totals"].reshape(-1), per_roll]).cpu()
+    return host[:MUSIC_FEATURES].tolist(), host[MUSIC_FEATURES:].reshape(len(MUSIC_SCALARS), -1)
+
+
+def compare_music(a, b) -> dict:
+    """How far two sets of rolls are apart as music (two MusicStats; one read-back each).  For each distribution of music_summary
+    (``pitch_class``, ``pitch_class_onsets``, ``duration``, ``polyphony``, ``ioi``): ``js_<name>``, the Jensen-Shannon divergence in
+    bits (0 identical, 1 disjoint), and ``overlap_<name>`` = sum of min(p, q); both nan when either side has no count.  For each
+    per-roll number (``notes``, ``cells``, ``used_pitches``, ``pitch_range``, ``max_polyphony``; an empty roll counts with 0):
+    ``mean_<name>_a``, ``mean_<name>_b`` and ``w1_<name>``, the Wasserstein-1 distance of the two empirical distributions (the sum
+    over integers v of |F_a(v) - F_b(v)|); nan for a side without rolls.  And ``scale_consistency_a`` / ``_b``."""
+    (ta, ra), (tb, rb) = _music_host(a), _music_host(b)
+    out = {}
+    for name, source in MUSIC_DISTRIBUTIONS.items():
+        out[f"js_{name}"], out[f"overlap_{name}"] = _js_and_overlap(ta[MUSIC_COLUMNS[source]], tb[MUSIC_COLUMNS[source]])
+    for i, name in enumerate(MUSIC_SCALARS):
+        out[f"mean_{name}_a"] = _ratio(int(ra[i].sum()), ra.shape[1])
+        out[f"mean_{name}_b"] = _ratio(int(rb[i].sum()), rb.shape[1])
+        out[f"w1_{name}"] = _wasserstein1(ra[i], rb[i])
+    out["scale_consistency_a"] = _scale_consistency(ta[MUSIC_COLUMNS["pc_cells"]])[0]
+    out["scale_consistency_b"] = _scale_consistency(tb[MUSIC_COLUMNS["pc_cells"]])[0]
+    return out
+
+
+def sample_music_stats(model, dataset, num_samples, *, temperature=1.0, seed=None, prior=None, pitch_offset=0, batch_size=256,
+                       **note_kwargs) -> dict:
+    """Does what the model generates behave like the training set as music?  ``model.sample_notes(num_samples, temperature=...,
+    seed=..., cleaned=True, **note_kwargs)`` (``prior``: a ``mixture.LatentMixture`` to draw the latents from), music_statistics of
+    the cleaned planes and of ``dataset`` (a ``PianorollDataset`` with "bits" storage on the device, of the model's height).  A
+    dataset whose rolls are wider than the model's input is reduced to the centre window of the model's width first, in batches
+    of ``batch_size`` through ``data.gather_rolls`` and ``binarize_rolls`` into a MusicStatsAccumulator.  Returns
+    ``{"samples": music_summary, "dataset": music_summary, "gap": compare_music(samples, dataset)}``."""
+    from .data import PianorollDataset, gather_rolls
+    if not isinstance(dataset, PianorollDataset):
+        raise TypeError("dataset must be a PianorollDataset")
+    if dataset.storage != "bits":
+        raise ValueError(f"the dataset must have 'bits' storage, got {dataset.storage!r}")
+    if dataset.pinned or not dataset.data.is_cuda:
+        raise ValueError("the dataset must be on the device, not in pinned host memory")
+    size = int(model.img_size)
+    if dataset.height != size or dataset.width < size:
+        raise ValueError(f"the dataset's rolls are {dataset.height}x{dataset.width}, the model's {size}x{size}")
+    if isinstance(batch_size, bool) or int(batch_size) != batch_size or batch_size < 1:
+        raise ValueError(f"batch_size must be an integer >= 1, got {batch_size}")
+    off = _music_pitch_offset(pitch_offset)
+    if prior is not None:
+        note_kwargs = dict(note_kwargs, prior=prior)
+    notes = model.sample_notes(int(num_samples), temperature=temperature, seed=seed, cleaned=True, **note_kwargs)
+    samples = music_statistics(notes["cleaned"], pitch_offset=off)
+    if dataset.width == size:
+        data = music_statistics(dataset, pitch_offset=off)
+    else:
+        acc = MusicStatsAccumulator(off)
+        for first in range(0, len(dataset), int(batch_size)):
+            acc.update(gather_rolls(dataset.data, dataset.kind, size, first=first, batch=min(int(batch_size), len(dataset) - first),
+                                    crop_mode=_lib.CROP_CENTRE))
+        data = acc.compute()
+    return {"samples": music_summary(samples), "dataset": music_summary(data), "gap": compare_music(samples, data)}
+
+
 def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nll_samples=0, latent_rolls=0, note_thresholds=None,
-             note_events=None):
+             note_events=None, music_stats=False):
     """nll_samples = K > 0 adds ``nll`` (mean over the samples of -log p(x), importance-weighted with K draws) and ``elbo``
     (mean per-sample ELBO), both in nats per roll (VanillaVAE.log_likelihood); 0 leaves keys, values and printout as the
     reference has them.  latent_rolls = R > 0 keeps the eval forward's own mu / log_var of the first R rolls (loader order)
@@ -428,6 +702,9 @@ def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nl
     reconstruction with those keywords and of the stimuli by plain thresholding at ``target_threshold``, matches them
     (note_event_metrics) and adds ``notes_pred``, ``notes_true``, ``matched`` (counts over the pass) and ``note_precision``,
     ``note_recall``, ``note_f1`` (fractions); None leaves results and launches as they are.
+    music_stats = True accumulates the musical statistics (music_statistics, cut at 0.5) of the reconstructions and of the stimuli
+    during the pass, two library calls per batch and nothing read back until the end, and adds the keys of
+    ``compare_music(reconstructions, stimuli)`` prefixed ``music_``; False leaves results and launches as they are.
     Under torch.distributed each rank reports its own shard."""
     if note_events is not None:
         from .generation import extract_notes
@@ -438,6 +715,7 @@ def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nl
             raise ValueError(f"note_events has unknown keys {sorted(unknown)}")
         ne_counts = [0, 0, 0]
     notes = None if note_thresholds is None else ReconMetricsAccumulator(note_thresholds, device=device)
+    music = (MusicStatsAccumulator(), MusicStatsAccumulator()) if music_stats else None
     if isinstance(latent_rolls, bool) or int(latent_rolls) != latent_rolls or latent_rolls < 0:
         raise ValueError(f"latent_rolls must be an integer >= 0, got {latent_rolls}")
     model.eval()
@@ -468,6 +746,9 @@ def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nl
             nll_sum -= lk["log_likelihood"].sum()
             elbo_sum += lk["elbo"].sum()
         rec = output["output"]
+        if music is not None:
+            music[0].update(rec.float())
+            music[1].update(stimuli.float())
         if note_events is not None:
             got = extract_notes(rec, **ne_kw)
             want = extract_notes(stimuli.float().contiguous(), onset_threshold=ne_tt)
@@ -515,10 +796,14 @@ def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nl
             results[k] = ls[k] if k == "active_units" else float(ls[k])
     if note_events is not None:
         results.update(note_event_ratios(*ne_counts))
+    if music is not None and n_seen:
+        results.update({f"music_{k}": v for k, v in compare_music(music[0].compute(), music[1].compute()).items()})
     if verbosity >= 1:
         print(f"\n{partition_name} evaluation results:")
         for k, v in results.items():
-            if k in ("note_precision", "note_recall", "note_f1"):
+            if k.startswith("music_"):
+                print(f"  {k + ' ':.<36s} {v:9.5f}")
+            elif k in ("note_precision", "note_recall", "note_f1"):
                 print(f"  {k + ' ':.<24s} {100.0 * v:6.2f} %")
             elif "count" in k or k == "active_units" or k in ("notes_pred", "notes_true", "matched"):
                 print(f"  {k + ' ':.<21s}{v:7d}")

@@ -79,3 +79,12 @@ class NoteEvents(TypedDict):
     offsets: Tensor           # [n + 1] int64: roll r's events are events[offsets[r]:offsets[r + 1]]
     cleaned: Tensor | None    # [n, h, w/8] uint8: the kept cells as bit planes, numpy.packbits order
     total: Tensor             # 0-d int64 view of offsets[n]: the number of events, whatever the capacity
+
+
+class MusicStats(TypedDict):
+    features: Tensor          # [n, 76] int32: one row of counts per roll (include/vae_music.h has the table)
+    totals: Tensor            # [76] int64: the column sums; `lowest` the minimum over non-empty rolls, `highest` / `max_polyphony` maxima
+    columns: dict             # name -> slice of the 76 columns (evaluation.MUSIC_COLUMNS)
+    height: int               # pitch rows of a roll
+    width: int                # time steps of a roll
+    pitch_offset: int         # the pitch of row 0: row p has pitch class (p + pitch_offset) mod 12
