@@ -19,7 +19,7 @@ from .types_helpers import EncoderOutput, LossOutput, ModelOutput  # noqa: F401,
 
 __all__ = ["VanillaVAE", "FusedAdamW", "train_one_epoch", "build_optimizer", "SyntheticPianorollLoader", "PianorollDataset",
            "DevicePianorollLoader", "epoch_indices", "gather_rolls", "augmentation_params", "extract_notes", "binarize_rolls",
-           "events_to_lists", "nearest_rolls", "novelty_summary", "sample_novelty"]
+           "events_to_lists", "nearest_rolls", "novelty_summary", "sample_novelty", "compare_encodings", "sample_fidelity"]
 
 
 def __getattr__(name):
@@ -35,6 +35,9 @@ def __getattr__(name):
     if name in ("nearest_rolls", "novelty_summary", "sample_novelty"):
         from . import evaluation
         return getattr(evaluation, name)
+    if name in ("compare_encodings", "sample_fidelity"):
+        from . import fidelity
+        return getattr(fidelity, name)
     if name == "safe_save_model":
         from .utils import safe_save_model
         return safe_save_model

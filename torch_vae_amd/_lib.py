@@ -1,5 +1,5 @@
-"""ctypes binding of the C-ABI library (include/vae_step.h, include/vae_mixture.h for the latent mixture and include/vae_music.h
-for the musical statistics).
+"""ctypes binding of the C-ABI library (include/vae_step.h, include/vae_mixture.h for the latent mixture, include/vae_music.h
+for the musical statistics and include/vae_fidelity.h for the set-level fidelity metrics).
 
 The product path has no CPU fallback: if the HIP library is missing this module
 raises at import of the first symbol, loudly.
@@ -47,6 +47,8 @@ MIXTURE_MAX_COMPONENTS, MIXTURE_MAX_DIM_FULL, MIXTURE_MAX_DIM_DIAG = 64, 128, 40
 MIXTURE_STREAM_U, MIXTURE_STREAM_EPS = 811, 812
 # include/vae_music.h: the width of a feature row; the limits of vae_music_roll_stats
 MUSIC_FEATURES, MUSIC_MAX_ROLL_BYTES, MUSIC_MAX_PITCH_OFFSET = 76, 8192, 1 << 20
+# include/vae_fidelity.h: the limits on the dimension, k, the bandwidths, the splits and a set's size
+FID_MAX_DIM, FID_MAX_K, FID_MAX_BANDWIDTHS, FID_MAX_SPLITS, FID_MAX_POINTS = 128, 8, 8, 64, 1 << 22
 
 PARAM_NAMES = (
     [f"encoder.{i}.{j}" for i in range(4) for j in ("0.weight", "0.bias", "1.weight", "1.bias")]
@@ -151,6 +153,10 @@ def lib():
     _sig(L.vae_mixture_em, i32, [p, i64, i32, i32, i32, i32, f64, p, p, p, p, p, p, p, p, p, p])
     # include/vae_music.h
     _sig(L.vae_music_roll_stats, i32, [p, i64, i32, i32, i32, p, p, i32, p])
+    # include/vae_fidelity.h
+    _sig(L.vae_fidelity_knn_radii, i32, [p, i64, i32, i32, i32, p, p])
+    _sig(L.vae_fidelity_balls, i32, [p, i64, p, i64, i32, p, i32, i32, p, p, p, p])
+    _sig(L.vae_fidelity_kernel_sums, i32, [p, i64, p, i64, i32, p, i32, i32, i32, p, p])
     _lib = L
     return L
 
@@ -174,6 +180,9 @@ MIXTURE_EXPORTS = ["vae_mixture_factor", "vae_mixture_log_prob", "vae_mixture_ms
 
 # include/vae_music.h (its own header too)
 MUSIC_EXPORTS = ["vae_music_roll_stats"]
+
+# include/vae_fidelity.h (and this one)
+FIDELITY_EXPORTS = ["vae_fidelity_knn_radii", "vae_fidelity_balls", "vae_fidelity_kernel_sums"]
 
 
 def check(rc: int, what: str = ""):
