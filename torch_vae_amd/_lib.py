@@ -1,5 +1,6 @@
 """ctypes binding of the C-ABI library (include/vae_step.h, include/vae_mixture.h for the latent mixture, include/vae_music.h
-for the musical statistics and include/vae_fidelity.h for the set-level fidelity metrics).
+for the musical statistics, include/vae_fidelity.h for the set-level fidelity metrics and include/vae_attributes.h for the
+attribute-regularised latents).
 
 The product path has no CPU fallback: if the HIP library is missing this module
 raises at import of the first symbol, loudly.
@@ -49,6 +50,10 @@ MIXTURE_STREAM_U, MIXTURE_STREAM_EPS = 811, 812
 MUSIC_FEATURES, MUSIC_MAX_ROLL_BYTES, MUSIC_MAX_PITCH_OFFSET = 76, 8192, 1 << 20
 # include/vae_fidelity.h: the limits on the dimension, k, the bandwidths, the splits and a set's size
 FID_MAX_DIM, FID_MAX_K, FID_MAX_BANDWIDTHS, FID_MAX_SPLITS, FID_MAX_POINTS = 128, 8, 8, 64, 1 << 22
+# include/vae_attributes.h: the counters of a roll (in this order), the attributes made of them (name -> VAE_ATTR_* number) and the limits
+ATTR_COUNTERS = ("cells", "notes", "used_pitches", "lowest", "highest", "sounding_steps", "onset_steps", "pitch_sum")
+ATTRIBUTES = {"note_density": 0, "note_count": 1, "pitch_range": 2, "mean_pitch": 3, "polyphony": 4, "onset_steps": 5, "used_pitches": 6}
+ATTR_MAX_PAIRS, ATTR_MAX_BATCH, ATTR_MAX_DIM, ATTR_MAX_ROWS, ATTR_MAX_CELLS, ATTR_MAX_POINTS = 8, 4096, 4096, 1024, 1 << 20, 65536
 
 PARAM_NAMES = (
     [f"encoder.{i}.{j}" for i in range(4) for j in ("0.weight", "0.bias", "1.weight", "1.bias")]
@@ -157,6 +162,11 @@ def lib():
     _sig(L.vae_fidelity_knn_radii, i32, [p, i64, i32, i32, i32, p, p])
     _sig(L.vae_fidelity_balls, i32, [p, i64, p, i64, i32, p, i32, i32, p, p, p, p])
     _sig(L.vae_fidelity_kernel_sums, i32, [p, i64, p, i64, i32, p, i32, i32, i32, p, p])
+    # include/vae_attributes.h (attr / dim: host arrays of int32)
+    i32p = C.POINTER(C.c_int32)
+    _sig(L.vae_attr_roll_counters, i32, [p, i64, i32, i32, f32, p, p])
+    _sig(L.vae_attr_regularizer, i32, [p, i32, i32, p, i32, i32, i32p, i32p, f32, f32, p, p, p])
+    _sig(L.vae_attr_concordance, i32, [p, i32, i32, p, i64, i32, i32p, p, p, p, p])
     _lib = L
     return L
 
@@ -183,6 +193,9 @@ MUSIC_EXPORTS = ["vae_music_roll_stats"]
 
 # include/vae_fidelity.h (and this one)
 FIDELITY_EXPORTS = ["vae_fidelity_knn_radii", "vae_fidelity_balls", "vae_fidelity_kernel_sums"]
+
+# include/vae_attributes.h (and this one)
+ATTR_EXPORTS = ["vae_attr_roll_counters", "vae_attr_regularizer", "vae_attr_concordance"]
 
 
 def check(rc: int, what: str = ""):

@@ -10,6 +10,7 @@ import math
 import torch
 
 from . import _lib
+from .attributes import ATTRIBUTE_NAMES, attribute_correlation, attribute_values, roll_attributes  # noqa: F401  (part of this module's surface)
 from .types_helpers import LatentStatsOutput, MusicStats, NearestRolls, ReconMetricsOutput
 
 MAX_LATENT_DIM = 4096
@@ -685,7 +686,7 @@ def sample_music_stats(model, dataset, num_samples, *, temperature=1.0, seed=Non
 
 
 def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nll_samples=0, latent_rolls=0, note_thresholds=None,
-             note_events=None, music_stats=False):
+             note_events=None, music_stats=False, attributes=False):
     """nll_samples = K > 0 adds ``nll`` (mean over the samples of -log p(x), importance-weighted with K draws) and ``elbo``
     (mean per-sample ELBO), both in nats per roll (VanillaVAE.log_likelihood); 0 leaves keys, values and printout as the
     reference has them.  latent_rolls = R > 0 keeps the eval forward's own mu / log_var of the first R rolls (loader order)
@@ -705,6 +706,10 @@ def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nl
     music_stats = True accumulates the musical statistics (music_statistics, cut at 0.5) of the reconstructions and of the stimuli
     during the pass, two library calls per batch and nothing read back until the end, and adds the keys of
     ``compare_music(reconstructions, stimuli)`` prefixed ``music_``; False leaves results and launches as they are.
+    attributes = True keeps the eval forward's own means and the attribute counters of the stimuli (roll_attributes, cut at the
+    model's ``attr_threshold``; the first 65536 rolls) on the device and adds the Kendall tau-b ``attr_tau_<name>`` between attribute
+    and latent dimension for every pair of ``model.attr_reg`` - or, when that is None, for all seven attributes, each against the
+    dimension whose |tau| is largest (NaN when every dimension is constant); False leaves results and launches as they are.
     Under torch.distributed each rank reports its own shard."""
     if note_events is not None:
         from .generation import extract_notes
@@ -716,6 +721,7 @@ def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nl
         ne_counts = [0, 0, 0]
     notes = None if note_thresholds is None else ReconMetricsAccumulator(note_thresholds, device=device)
     music = (MusicStatsAccumulator(), MusicStatsAccumulator()) if music_stats else None
+    attr_mu, attr_counters, attr_n = [], [], 0
     if isinstance(latent_rolls, bool) or int(latent_rolls) != latent_rolls or latent_rolls < 0:
         raise ValueError(f"latent_rolls must be an integer >= 0, got {latent_rolls}")
     model.eval()
@@ -745,6 +751,11 @@ def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nl
             lk = model.log_likelihood(stimuli, nll_samples)
             nll_sum -= lk["log_likelihood"].sum()
             elbo_sum += lk["elbo"].sum()
+        if attributes and attr_n < _lib.ATTR_MAX_POINTS:
+            k = min(_lib.ATTR_MAX_POINTS - attr_n, stimuli.shape[0])
+            attr_mu.append(output["encoded"]["mu"][:k].detach().float().clone())
+            attr_counters.append(roll_attributes(stimuli[:k].float(), getattr(model, "attr_threshold", 0.5)))
+            attr_n += k
         rec = output["output"]
         if music is not None:
             music[0].update(rec.float())
@@ -798,10 +809,20 @@ def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nl
         results.update(note_event_ratios(*ne_counts))
     if music is not None and n_seen:
         results.update({f"music_{k}": v for k, v in compare_music(music[0].compute(), music[1].compute()).items()})
+    if attributes and attr_n:
+        reg = getattr(model, "attr_reg", None)
+        names = list(reg) if reg is not None else list(ATTRIBUTE_NAMES)
+        tau = attribute_correlation(torch.cat(attr_mu), torch.cat(attr_counters), names)
+        for k, name in enumerate(names):
+            if reg is not None:
+                results[f"attr_tau_{name}"] = float(tau[k, reg[name]])
+            else:
+                mag = torch.nan_to_num(tau[k].abs(), nan=-1.0)
+                results[f"attr_tau_{name}"] = float(tau[k, int(mag.argmax())])
     if verbosity >= 1:
         print(f"\n{partition_name} evaluation results:")
         for k, v in results.items():
-            if k.startswith("music_"):
+            if k.startswith("music_") or k.startswith("attr_tau_"):
                 print(f"  {k + ' ':.<36s} {v:9.5f}")
             elif k in ("note_precision", "note_recall", "note_f1"):
                 print(f"  {k + ' ':.<24s} {100.0 * v:6.2f} %")

@@ -154,3 +154,33 @@ def interpolate_latents(z_a: torch.Tensor, z_b: torch.Tensor, steps: int, mode: 
     so = torch.sin(torch.where(flat, torch.ones_like(omega), omega))
     slerp = torch.sin((1.0 - t) * omega) / so * a + torch.sin(t * omega) / so * b
     return torch.where(flat, lerp, slerp).to(z_a.dtype)
+
+
+def traverse(model, z, dim, values, threshold=0.5):
+    """Decode ``z`` [n, latent_dim] with latent dimension ``dim`` replaced by each of ``values`` (a sequence or 1-D tensor of
+    ``steps`` numbers) - with a model trained under ``attr_reg={attribute: dim}`` this turns the attribute up and down while the rest
+    of the phrase stays.  Decoded with running statistics (eval mode, the model untouched).  Returns
+    ``(rolls [n, steps, 1, H, W], counters [n, steps, 8])`` on the device, the counters ``attributes.roll_attributes`` of the rolls
+    cut at ``threshold``; nothing is read back."""
+    from .attributes import roll_attributes
+    model._require_device()
+    if not isinstance(z, torch.Tensor) or z.dim() != 2 or z.shape[1] != model.latent_dim:
+        raise ValueError(f"z must be a tensor [n, {model.latent_dim}], got {tuple(z.shape) if isinstance(z, torch.Tensor) else type(z)}")
+    if isinstance(dim, bool) or not isinstance(dim, int) or not 0 <= dim < model.latent_dim:
+        raise ValueError(f"dim must be a latent dimension in 0..{model.latent_dim - 1}, got {dim!r}")
+    dev = model._flat.device
+    on_device = isinstance(values, torch.Tensor) and values.is_cuda
+    values = values.detach().to(dev, torch.float32).reshape(-1) if on_device else [float(v) for v in torch.as_tensor(values).reshape(-1).tolist()]
+    n, steps = z.shape[0], len(values)
+    if steps < 1:
+        raise ValueError("values must hold at least one number")
+    zz = z.detach().to(dev, torch.float32)[:, None, :].repeat(1, steps, 1)
+    if on_device:
+        zz[:, :, dim] = values
+    else:       # host numbers go in as kernel arguments: a copy from pageable host memory would wait for the stream
+        for s, v in enumerate(values):
+            zz[:, s, dim].fill_(v)
+    with torch.no_grad():
+        rolls = model._run_decode(zz.view(n * steps, model.latent_dim), train=False)
+    counters = roll_attributes(rolls, threshold)
+    return rolls.view(n, steps, *rolls.shape[1:]), counters.view(n, steps, -1)

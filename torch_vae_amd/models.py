@@ -59,6 +59,22 @@ Deviations from the reference, all explicit:
     forward and fused step; batches of at most 4096.  ``total_correlation()``
     returns the value of the last forward.  Data parallel: TC is over the
     replica's OWN batch, as ``kl_d`` and the BatchNorm statistics are.
+  * ``attr_reg`` (keyword-only; default ``None`` = off) ties latent
+    dimensions to musical attributes of the input roll (Pati & Lerch 2020):
+    a dict ``{attribute: dimension}`` of up to 8 pairs, attributes
+    ``note_density``, ``note_count``, ``pitch_range``, ``mean_pitch``,
+    ``polyphony``, ``onset_steps``, ``used_pitches``, one attribute per
+    dimension.  The loss gains ``attr_weight * sum_r L_r`` with
+    ``L_r = mean_ij |tanh(attr_delta (z_i^r - z_j^r)) - sgn(a_i - a_j)|``
+    over the batch, the attributes counted from ``x >= attr_threshold`` on the
+    device (include/vae_attributes.h).  All four are attributes read at every
+    forward and fused step; batches of at most 4096; combines with every
+    reconstruction term, KL option and storage type.  ``attribute_loss()``
+    returns ``[sum_r L_r, L_1, ...]`` of the last step.  ``kld_loss`` and
+    ``reconstruction_loss`` are unchanged.  Data parallel: the replica's OWN
+    batch.  f16 storage: the gradient on z rides on the backward's
+    power-of-two scale; its entries are at most
+    ``attr_weight * 2 * attr_delta / B``.
 
   Reconstruction term of ``loss = reconstruction + kld_weight * T`` (mean over B*H*W):
 
@@ -91,6 +107,7 @@ import torch
 from torch import Tensor, nn
 
 from . import _lib
+from .attributes import AttributeTerm, attribute_regularizer, checked_attr_reg, roll_attributes
 from .types_helpers import EncoderOutput, LikelihoodOutput, LossOutput, ModelOutput
 
 _DTYPES = {"f32": _lib.DTYPE_F32, "fp32": _lib.DTYPE_F32, "float32": _lib.DTYPE_F32,
@@ -313,6 +330,10 @@ class VanillaVAE(nn.Module):
         kl_capacity: float | None = None,
         tc_weight: float | None = None,
         pos_weight: float | None = None,
+        attr_reg: dict | None = None,
+        attr_weight: float = 1.0,
+        attr_delta: float = 10.0,
+        attr_threshold: float = 0.5,
     ):
         super().__init__()
         if in_channels != 1:
@@ -341,6 +362,12 @@ class VanillaVAE(nn.Module):
         self.kl_free_bits = kl_free_bits
         self.kl_capacity = kl_capacity
         self.tc_weight = tc_weight
+        checked_attr_reg(attr_reg, embed_dim, attr_weight, attr_delta, attr_threshold)
+        self.attr_reg = attr_reg
+        self.attr_weight = attr_weight
+        self.attr_delta = attr_delta
+        self.attr_threshold = attr_threshold
+        self._attr_loss = None
         s = self.img_size // 16 if self.generalised else 2
         self.last_conv_size = s * s  # models.py:33 hard-wires 4
         self.flattened_size = self.last_conv_size * hidden_dims[-1]
@@ -882,6 +909,13 @@ class VanillaVAE(nn.Module):
                                             output["encoded"]["log_var"], self.kld_weight,
                                             _recon_setting(self.recon_loss, getattr(self, "pos_weight", None)),
                                             _kl_objective(self.kl_free_bits, self.kl_capacity))
+        if getattr(self, "attr_reg", None) is not None:     # (off: the output is not looked at any further, as before)
+            z = output.get("latents") if hasattr(output, "get") else None
+            if z is None:
+                raise ValueError("loss() with attr_reg set needs output['latents']: the regulariser is a function of z")
+            attr = self._attr_setting(z.shape[0])
+            counters = roll_attributes(output["input"].detach().float(), attr[4])
+            loss = loss + AttributeTerm.apply(z if z.dtype == torch.float32 else z.float(), counters, self, attr)
         return LossOutput(loss=loss, reconstruction_loss=out3[1].detach(), kld_loss=out3[2].detach())
 
     def kl_per_dim(self) -> Tensor:
@@ -984,7 +1018,15 @@ class VanillaVAE(nn.Module):
             eps = torch.randn(x.shape[0], self.latent_dim, device=x.device, dtype=torch.float32)
         # train = 2: the library may leave the output conv / sigmoid / BCE to the backward (one kernel for the layer's
         # forward and backward): xhat and the ELBO scalars are then written by the backward call below
+        attr = self._attr_setting(x.shape[0])    # (None: not one launch or byte below differs from the step without the option)
         xhat, mu, lv, z, _ = self._run_forward(x, eps, train=True, want_pre=False, defer_output=True)
+        g_z = 0
+        if attr is not None:
+            # the regulariser of this forward's own z, in line on the caller's stream: two small launches whose gradient the
+            # backward's latent kernel needs (csrc/edge_kernels.cuh: LatentBwdArgs::gz)
+            ids, dims, aw, delta, th = attr
+            self._attr_loss, g = attribute_regularizer(z, roll_attributes(self._last["x"], th), ids, dims, delta, aw)
+            g_z = g.data_ptr()
         out3 = torch.empty(3, device=x.device, dtype=torch.float32)
         # the ELBO scalars are only read after the step: finalised beside the backward (joined by it), not in front of it
         with self._device_guard():
@@ -994,13 +1036,33 @@ class VanillaVAE(nn.Module):
         for part in ((0,) if on_decoder_grads is None else (1, 2)):
             with self._device_guard():
                 _lib.check(_lib.lib().vae_backward_part(
-                    self._ctx.handle, last["x"].data_ptr(), self._flat.data_ptr(), self._gflat.data_ptr(), 0, 0, 0, 0, 0, 0,
+                    self._ctx.handle, last["x"].data_ptr(), self._flat.data_ptr(), self._gflat.data_ptr(), 0, 0, 0, 0, g_z, 0,
                     float(self.kld_weight), 1, part, self._stream()), "vae_backward")
             if part == 1:
                 self.bind_flat_grads()
                 on_decoder_grads()
         self.bind_flat_grads()
+        if attr is not None:
+            out3[0].add_(self._attr_loss[0], alpha=attr[2])    # (behind the backward, which joins the deferred ELBO scalars)
         return out3, xhat
+
+    # -- attribute regularisation (include/vae_attributes.h) ---------------------------------------------------------
+    def _attr_setting(self, batch: int):
+        """None with attr_reg off, else (attribute numbers, dimensions, weight, delta, threshold); ValueError on a bad value."""
+        reg = getattr(self, "attr_reg", None)
+        if reg is None:
+            return None
+        return checked_attr_reg(reg, self.latent_dim, getattr(self, "attr_weight", 1.0), getattr(self, "attr_delta", 10.0),
+                                getattr(self, "attr_threshold", 0.5), batch)
+
+    def attribute_loss(self) -> Tensor:
+        """The attribute regulariser of the model's last step with ``attr_reg`` set (fused_forward_backward, fused_step or
+        loss()): a float64 device tensor ``[1 + pairs]`` - the unweighted sum, then L_r of every pair in ``attr_reg``'s order - with
+        no host synchronisation."""
+        self._require_device()
+        if getattr(self, "_attr_loss", None) is None:
+            raise RuntimeError("attribute_loss needs a step or loss() of this model with attr_reg set")
+        return self._attr_loss
 
 
     # -- the whole training step as ONE library call ------------------------------------------------------------

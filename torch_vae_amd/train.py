@@ -150,6 +150,8 @@ def fused_step(model: VanillaVAE, optimizer, x, eps=None, use_device_eps: bool =
     (+70 us with six hardware queues: event hand-offs and a sixth stream; with eight queues the whole step runs 2.5x
     slower, which this function refuses), so it is opt-in: ``overlap=True`` or VAE_DP_OVERLAP=1."""
     one_call = isinstance(optimizer, FusedAdamW) and os.environ.get("VAE_ONE_CALL_STEP", "1") != "0"
+    if getattr(model, "attr_reg", None) is not None:
+        one_call = False      # the attribute regulariser sits between forward and backward: the split path (the one-call step has no such hook)
     if one_call:
         optimizer._bind()
         one_call = optimizer._model is model and len(optimizer.param_groups) == len(optimizer._ranges)
@@ -307,6 +309,12 @@ def train_one_epoch(config, model, optimizer, scheduler, criterion, dataloader, 
         model.tc_weight = config.kl_tc_weight
     if getattr(config, "recon_pos_weight", None) is not None:   # positive-class weight of the BCE term (VanillaVAE.pos_weight), both step paths
         model.pos_weight = config.recon_pos_weight
+    if getattr(config, "attr_reg", None) is not None:   # attribute-regularised latent dimensions (VanillaVAE.attr_reg), both step paths
+        model.attr_reg = dict(config.attr_reg)
+    if getattr(config, "attr_weight", None) is not None:
+        model.attr_weight = config.attr_weight
+    if getattr(config, "attr_delta", None) is not None:
+        model.attr_delta = config.attr_delta
     if isinstance(dataloader, DevicePianorollLoader):   # its order and augmentation draws are functions of (seed, epoch)
         dataloader.set_epoch(epoch)
     n_batches = len(dataloader)
