@@ -156,6 +156,16 @@ int vae_set_recon_loss(vae_ctx* ctx, int kind);
  * nothing: it may be called every step.  Returns -1 for an unknown kind, a pos_weight that is NaN, infinite, <= 0 or > 1024, or a
  * non-zero param with BCE / MSE.  (vae_set_recon_loss itself keeps refusing every kind but BCE / MSE.) */
 int vae_set_recon_loss_ex(vae_ctx* ctx, int kind, double param);
+/* A reconstruction target apart from the input, for the NEXT forward of this context only (denoising and infilling: x is the
+ * corrupted roll the encoder sees, target the clean one the reconstruction term is taken against).  target [B,1,H,W] f32 with the
+ * layout, residency and alignment of that forward's x; the caller keeps it alive as long as x, until the backward of that forward
+ * has passed (a train = 2 forward reads it in the backward).  One-shot: whichever forward comes next takes the setting out of the
+ * context, and only a full forward uses it - vae_forward, vae_train_step, vae_train_step_fused and vae_train_step_fused_clipped;
+ * vae_encode, vae_decode and vae_log_likelihood consume and ignore it.  The forward records the pointer: every output-conv kernel
+ * (in the forward, or deferred into the backward), and with them vae_loss / vae_loss_deferred and the reconstruction gradient,
+ * then read target where they read x; the encoder, encoder.0's weight gradient and dx keep reading x.  Without the call (or with
+ * target = NULL, which clears a pending one) the target is x and nothing differs.  Enqueues nothing.  Returns -1 for a null ctx. */
+int vae_set_recon_target(vae_ctx* ctx, const float* target);
 /* vae_elbo_generic with the reconstruction term chosen per call (recon: VAE_RECON_*); for MSE g_xhat = (xhat - t) * 2/n. */
 int vae_elbo_generic_ex(const float* xhat, const float* target, const float* mu, const float* log_var, int64_t n,
                         int batch, int latent_dim, float kld_weight, int recon, float* out3, float* g_xhat,

@@ -19,7 +19,8 @@ from .types_helpers import EncoderOutput, LossOutput, ModelOutput  # noqa: F401,
 
 __all__ = ["VanillaVAE", "FusedAdamW", "train_one_epoch", "build_optimizer", "SyntheticPianorollLoader", "PianorollDataset",
            "DevicePianorollLoader", "epoch_indices", "gather_rolls", "augmentation_params", "extract_notes", "binarize_rolls",
-           "events_to_lists", "nearest_rolls", "novelty_summary", "sample_novelty", "compare_encodings", "sample_fidelity"]
+           "events_to_lists", "nearest_rolls", "novelty_summary", "sample_novelty", "compare_encodings", "sample_fidelity",
+           "corrupt_rolls", "corruption_spans", "infill"]
 
 
 def __getattr__(name):
@@ -47,7 +48,10 @@ def __getattr__(name):
     if name in ("PianorollDataset", "DevicePianorollLoader", "epoch_indices", "gather_rolls", "augmentation_params"):
         from . import data
         return getattr(data, name)
-    if name in ("extract_notes", "binarize_rolls", "events_to_lists", "interpolate_latents"):
+    if name in ("corrupt_rolls", "corruption_spans", "Corruption"):
+        from . import denoise
+        return getattr(denoise, name)
+    if name in ("extract_notes", "binarize_rolls", "events_to_lists", "interpolate_latents", "infill"):
         from . import generation
         return getattr(generation, name)
     raise AttributeError(name)

@@ -1,6 +1,6 @@
 """ctypes binding of the C-ABI library (include/vae_step.h, include/vae_mixture.h for the latent mixture, include/vae_music.h
-for the musical statistics, include/vae_fidelity.h for the set-level fidelity metrics and include/vae_attributes.h for the
-attribute-regularised latents).
+for the musical statistics, include/vae_fidelity.h for the set-level fidelity metrics, include/vae_attributes.h for the
+attribute-regularised latents and include/vae_denoise.h for the denoising corruption).
 
 The product path has no CPU fallback: if the HIP library is missing this module
 raises at import of the first symbol, loudly.
@@ -54,6 +54,9 @@ FID_MAX_DIM, FID_MAX_K, FID_MAX_BANDWIDTHS, FID_MAX_SPLITS, FID_MAX_POINTS = 128
 ATTR_COUNTERS = ("cells", "notes", "used_pitches", "lowest", "highest", "sounding_steps", "onset_steps", "pitch_sum")
 ATTRIBUTES = {"note_density": 0, "note_count": 1, "pitch_range": 2, "mean_pitch": 3, "polyphony": 4, "onset_steps": 5, "used_pitches": 6}
 ATTR_MAX_PAIRS, ATTR_MAX_BATCH, ATTR_MAX_DIM, ATTR_MAX_ROWS, ATTR_MAX_CELLS, ATTR_MAX_POINTS = 8, 4096, 4096, 1024, 1 << 20, 65536
+# include/vae_denoise.h: the counter-generator streams of note dropout, the time span and the spurious cells; the limits on h and w
+DENOISE_STREAM_DROP, DENOISE_STREAM_SPAN, DENOISE_STREAM_ADD = 902, 903, 904
+DENOISE_MAX_ROWS, DENOISE_MAX_COLS = 1 << 20, 1 << 20
 
 PARAM_NAMES = (
     [f"encoder.{i}.{j}" for i in range(4) for j in ("0.weight", "0.bias", "1.weight", "1.bias")]
@@ -106,6 +109,7 @@ def lib():
     _sig(L.vae_elbo_generic_ex, i32, [p, p, p, p, i64, i32, i32, f32, i32, p, p, p, p, p])
     _sig(L.vae_set_recon_loss, i32, [p, i32])
     _sig(L.vae_set_recon_loss_ex, i32, [p, i32, f64])
+    _sig(L.vae_set_recon_target, i32, [p, p])
     _sig(L.vae_set_kl_objective, i32, [p, i32, f64])
     _sig(L.vae_elbo_generic_kl, i32, [p, p, p, p, i64, i32, i32, f32, i32, i32, f64, p, p, p, p, p])
     _sig(L.vae_elbo_generic_w, i32, [p, p, p, p, i64, i32, i32, f32, i32, f64, i32, f64, p, p, p, p, p])
@@ -167,6 +171,9 @@ def lib():
     _sig(L.vae_attr_roll_counters, i32, [p, i64, i32, i32, f32, p, p])
     _sig(L.vae_attr_regularizer, i32, [p, i32, i32, p, i32, i32, i32p, i32p, f32, f32, p, p, p])
     _sig(L.vae_attr_concordance, i32, [p, i32, i32, p, i64, i32, i32p, p, p, p, p])
+    # include/vae_denoise.h
+    _sig(L.vae_denoise_corrupt, i32, [p, p, p, i64, i32, i32, f32, f64, i32, i32, f64, f32, p, u64, u64, u64, p])
+    _sig(L.vae_denoise_params, i32, [p, i64, i32, i32, i32, u64, u64, u64, p])
     _lib = L
     return L
 
@@ -174,7 +181,7 @@ def lib():
 EXPORTS = [
     "vae_last_error", "vae_abi_version", "vae_param_layout", "vae_bn_layout", "vae_create", "vae_destroy",
     "vae_workspace_bytes", "vae_forward", "vae_decode", "vae_pre_latents", "vae_last_eps", "vae_loss", "vae_loss_deferred", "vae_elbo_generic",
-    "vae_set_recon_loss", "vae_set_recon_loss_ex", "vae_elbo_generic_ex", "vae_set_kl_objective", "vae_elbo_generic_kl", "vae_elbo_generic_w", "vae_kl_per_dim", "vae_total_correlation", "vae_last_total_correlation", "vae_log_likelihood", "vae_latent_stats",
+    "vae_set_recon_loss", "vae_set_recon_loss_ex", "vae_set_recon_target", "vae_elbo_generic_ex", "vae_set_kl_objective", "vae_elbo_generic_kl", "vae_elbo_generic_w", "vae_kl_per_dim", "vae_total_correlation", "vae_last_total_correlation", "vae_log_likelihood", "vae_latent_stats",
     "vae_recon_metrics",
     "vae_backward", "vae_backward_part", "vae_encode", "vae_backward_ex", "vae_comm_stream", "vae_comm_unique_id", "vae_comm_init", "vae_comm_world",
     "vae_comm_destroy", "vae_allreduce_grads", "vae_broadcast_state", "vae_adamw_step", "vae_train_step", "vae_train_step_fused",
@@ -196,6 +203,9 @@ FIDELITY_EXPORTS = ["vae_fidelity_knn_radii", "vae_fidelity_balls", "vae_fidelit
 
 # include/vae_attributes.h (and this one)
 ATTR_EXPORTS = ["vae_attr_roll_counters", "vae_attr_regularizer", "vae_attr_concordance"]
+
+# include/vae_denoise.h (and this one)
+DENOISE_EXPORTS = ["vae_denoise_corrupt", "vae_denoise_params"]
 
 
 def check(rc: int, what: str = ""):

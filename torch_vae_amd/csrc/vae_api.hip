@@ -299,6 +299,7 @@ extern "C" int vae_forward(vae_ctx* c, const float* x, int B, const float* param
     hipStream_t st = (hipStream_t)stream;
     if (begin_forward(c, FwdRecord::FULL, B, train, st)) return -1;
     c->fwd.x = x; c->fwd.xhat = xhat; c->fwd.mu = mu; c->fwd.lv = lv; c->fwd.z = z;
+    if (!c->fwd.target) c->fwd.target = x;
     const int rc = VAE_DISPATCH(c->dtype, forward_impl, (c, x, B, params, bn_running, nbt, eps, seed, train, xhat, mu, lv, z, st));
     if (rc) drop_forward(c);
     return rc;
@@ -400,6 +401,12 @@ static int check_recon(const char* what, int kind, double param) {
     if (kind == VAE_RECON_WBCE) {
         if (!(param > 0.0) || !(param <= 1024.0)) return vae_set_error(what, "pos_weight must be a finite number in (0, 1024]");   // (a NaN fails both comparisons)
     } else if (param != 0.0) return vae_set_error(what, "the parameter must be 0 for VAE_RECON_BCE / VAE_RECON_MSE");
+    return 0;
+}
+// one-shot: begin_forward (vae_ctx.h) consumes it
+extern "C" int vae_set_recon_target(vae_ctx* c, const float* target) {
+    if (!c) return vae_set_error("vae_set_recon_target", "null ctx");
+    c->recon_target = target;
     return 0;
 }
 extern "C" int vae_set_recon_loss_ex(vae_ctx* c, int kind, double param) {

@@ -126,7 +126,8 @@ struct WgradKnobs { int wgs, cap_mb, tile, wide, wide_wgs, small_wgs = 1024, mid
 // Exactly two functions change which forward is held: begin_forward and drop_forward (below).  Besides them the record is written
 // where a forward's product is made or consumed: decode_impl (the output conv ran or was deferred), launch_kl_shape (kl_pending), launch_tc (tc_done),
 // backward_first (convout_pending / dlogit_valid / loss_out3), bwd_clear_stats (bwd_dirty), backward_impl (bwd_half_done),
-// vae_loss_deferred (loss_out3 / loss_kw of a deferred output conv) and launch_conv_pipe (walk_dir).
+// vae_loss_deferred (loss_out3 / loss_kw of a deferred output conv) and launch_conv_pipe (walk_dir).  target: begin_forward moves the
+// context's pending vae_set_recon_target into it (a FULL forward only; null otherwise), and vae_forward fills in x where none was pending.
 struct FwdRecord {
     enum Kind { NONE, FULL, ENCODE, DECODE };   // FULL: vae_forward and the training steps; vae_backward_ex differentiates whichever it was
     Kind kind = NONE;
@@ -139,6 +140,9 @@ struct FwdRecord {
     int kl_reduced = 0;                          // kl_shape_kernel ran for this forward: kl_d and KL are in kl_ws (behind ev_kl)
     int tc_done = 0;                             // this forward's total correlation and its gradient are in tc_ws (launch_tc; behind ev_kl as well)
     const float* x = nullptr; float *xhat = nullptr, *mu = nullptr, *lv = nullptr, *z = nullptr;   // the caller's tensors (null: the kind has none)
+    // what the reconstruction term is taken against (vae_set_recon_target; x itself by default): read by every output-conv kernel, in the
+    // forward or deferred into the backward.  The encoder, conv1_wgrad and dx read x.  FULL forwards only: null for the other kinds.
+    const float* target = nullptr;
     // f16 storage: the backward runs on gradients multiplied by gmul (a power of two chosen per forward so that the stored
     // dz stay inside the f16 range: the BCE mean makes them O(1/(B*H*W))); every parameter gradient is written times ginv.
     // The backward is linear in the upstream gradient, so this changes no f32 result (powers of two are exact).  1 otherwise.
@@ -206,6 +210,7 @@ struct vae_ctx {
     WgradKnobs wk;
     // ---- settings for the forwards that follow (vae_set_recon_loss[_ex], vae_set_kl_objective); a forward snapshots them into its record ----
     int recon = VAE_RECON_BCE, kl_kind = VAE_KL_PLAIN; double kl_param = 0.0; double recon_param = 0.0;
+    const float* recon_target = nullptr;   // vae_set_recon_target: one-shot, consumed (and cleared) by the next begin_forward
     // ---- the last forward ----
     FwdRecord fwd;
     // ---- diagnostics: phase stamps (vae_debug_stamps) and per-kernel timing (bench.py roofline: HIP events on the launch stream) ----
@@ -288,6 +293,7 @@ static inline int begin_forward(vae_ctx* c, FwdRecord::Kind kind, int B, int tra
     const bool elbo = kind == FwdRecord::FULL;   // (no ELBO follows an encoder-only or decoder-only pass)
     f.kl_kind = elbo ? c->kl_kind : VAE_KL_PLAIN; f.kl_param = elbo ? c->kl_param : 0.0;
     f.x = nullptr; f.xhat = f.mu = f.lv = f.z = nullptr;
+    f.target = elbo ? c->recon_target : nullptr; c->recon_target = nullptr;   // one-shot: whichever forward comes next consumes it, only a FULL one uses it
     if (kind != FwdRecord::DECODE) f.walk_dir = 1;   // (a pass through the encoder restarts the alternating tile walk)
     set_grad_scale(c, B);
     return 0;

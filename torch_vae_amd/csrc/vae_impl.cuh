@@ -587,7 +587,7 @@ int forward_impl(vae_ctx* c, const float* x, int B, const float* params, float* 
     if (c->fwd.kl_kind != VAE_KL_PLAIN && launch_kl_shape(c, st)) return -1;
     // total-correlation objective: the pairwise pass and its backward follow on the same side stream
     if (c->fwd.kl_kind == VAE_KL_TC && launch_tc(c, st)) return -1;
-    return decode_impl<T>(c, z, B, params, bn_running, nbt, train, x, xhat, st);
+    return decode_impl<T>(c, z, B, params, bn_running, nbt, train, c->fwd.target, xhat, st);
 }
 
 
@@ -777,7 +777,7 @@ static int backward_first(vae_ctx* c, const float* x, const float* params, float
             if (step7 && c->use_convout_stream && H == cos::RW) {
                 // row-streaming form: units = (image, band of RB rows); a band costs RB/2 + 3 ticks and restages 4 rows
                 ConvOutStreamArgs<T> m; m.fuse = c->fwd.pending_f7;
-                m.yf = reinterpret_cast<const T*>(c->lay[7].y); m.wt = c->wout_t; m.bias = params + c->poff[39]; m.target = c->fwd.x;
+                m.yf = reinterpret_cast<const T*>(c->lay[7].y); m.wt = c->wout_t; m.bias = params + c->poff[39]; m.target = c->fwd.target;
                 m.xhat = c->fwd.xhat; m.accum = c->accum; m.dz = reinterpret_cast<T*>(c->lay[7].dz); m.slab = a.slab; m.stat = a.stat;
                 m.B = B; m.H = H; m.inv_n = (float)(1.0 / ((double)B * H * H)); m.slope = kSlope; m.gmul = c->fwd.gmul; m.recon_w = (float)c->fwd.recon_param;
                 m.dbg = (c->dbg_buf && !strcmp(c->dbg_tag, "final_layer.3")) ? c->dbg_buf : nullptr;
@@ -790,7 +790,7 @@ static int backward_first(vae_ctx* c, const float* x, const float* params, float
             }
             else if (step7) {
                 ConvOutStepArgs<T> m; m.fuse = c->fwd.pending_f7; m.rev = (c->knob_rev >> 1) & 1;
-                m.yf = reinterpret_cast<const T*>(c->lay[7].y); m.wt = c->wout_t; m.bias = params + c->poff[39]; m.target = c->fwd.x;
+                m.yf = reinterpret_cast<const T*>(c->lay[7].y); m.wt = c->wout_t; m.bias = params + c->poff[39]; m.target = c->fwd.target;
                 m.xhat = c->fwd.xhat; m.accum = c->accum; m.dz = reinterpret_cast<T*>(c->lay[7].dz); m.slab = a.slab; m.stat = a.stat;
                 m.B = B; m.H = H; m.W = H; m.n_tiles = B * (H / 8) * (H / 32);
                 m.inv_n = (float)(1.0 / ((double)B * H * H)); m.slope = kSlope; m.gmul = c->fwd.gmul; m.recon_w = (float)c->fwd.recon_param; m.ablate = c->knob_ablate_f;

@@ -164,6 +164,19 @@ def reconstruction_metrics(xhat, target, thresholds=(0.5,), *, target_threshold=
         roll_tp=roll_counts[:, 1::2], roll_fp=roll_counts[:, 2::2])
 
 
+def infill_metrics(xhat, target, t0, t1, thresholds=(0.5,), *, target_threshold=0.5) -> ReconMetricsOutput:
+    """``reconstruction_metrics`` on the time span ``[t0, t1)`` only - the columns ``generation.infill`` filled: xhat and target are
+    float32 GPU tensors [N, ..., W]; their last dimension is cut to the span (a strided view made contiguous: plumbing) and the
+    same HIP pass scores it."""
+    from .generation import checked_time_span
+    if not isinstance(xhat, torch.Tensor) or not isinstance(target, torch.Tensor):
+        raise TypeError("xhat and target must be tensors")
+    if xhat.dim() < 2 or tuple(xhat.shape) != tuple(target.shape):
+        raise ValueError(f"xhat and target must have the same shape [N, ..., W], got {tuple(xhat.shape)} and {tuple(target.shape)}")
+    t0, t1 = checked_time_span(t0, t1, xhat.shape[-1])
+    return reconstruction_metrics(xhat[..., t0:t1], target[..., t0:t1], thresholds, target_threshold=target_threshold)
+
+
 class ReconMetricsAccumulator:
     """reconstruction_metrics over a whole pass: update() adds a batch to totals that stay on the device (one library call, no host
     synchronisation, no allocation beyond the per-roll work space, which is reused while the batch size stays the same); compute()
@@ -686,7 +699,7 @@ def sample_music_stats(model, dataset, num_samples, *, temperature=1.0, seed=Non
 
 
 def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nll_samples=0, latent_rolls=0, note_thresholds=None,
-             note_events=None, music_stats=False, attributes=False):
+             note_events=None, music_stats=False, attributes=False, infill_span=None):
     """nll_samples = K > 0 adds ``nll`` (mean over the samples of -log p(x), importance-weighted with K draws) and ``elbo``
     (mean per-sample ELBO), both in nats per roll (VanillaVAE.log_likelihood); 0 leaves keys, values and printout as the
     reference has them.  latent_rolls = R > 0 keeps the eval forward's own mu / log_var of the first R rolls (loader order)
@@ -710,6 +723,10 @@ def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nl
     model's ``attr_threshold``; the first 65536 rolls) on the device and adds the Kendall tau-b ``attr_tau_<name>`` between attribute
     and latent dimension for every pair of ``model.attr_reg`` - or, when that is None, for all seven attributes, each against the
     dimension whose |tau| is largest (NaN when every dimension is constant); False leaves results and launches as they are.
+    infill_span = (t0, t1) runs, for every batch, ``generation.infill`` on the stimuli - a second eval pass on the batch with those
+    columns zeroed, decoded from the posterior mean, so no noise is drawn and every other result keeps its bits - scores the span's
+    columns against the stimuli (infill_metrics, both cut at 0.5) and adds ``infill_f1``, ``infill_precision`` and
+    ``infill_recall`` (percent); None leaves results and launches as they are.
     Under torch.distributed each rank reports its own shard."""
     if note_events is not None:
         from .generation import extract_notes
@@ -722,6 +739,13 @@ def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nl
     notes = None if note_thresholds is None else ReconMetricsAccumulator(note_thresholds, device=device)
     music = (MusicStatsAccumulator(), MusicStatsAccumulator()) if music_stats else None
     attr_mu, attr_counters, attr_n = [], [], 0
+    infill_acc = None
+    if infill_span is not None:
+        from .generation import checked_time_span, infill
+        if not isinstance(infill_span, (tuple, list)) or len(infill_span) != 2:
+            raise ValueError(f"infill_span must be a pair (t0, t1), got {infill_span!r}")
+        it0, it1 = checked_time_span(infill_span[0], infill_span[1], getattr(model, "img_size", infill_span[1]))
+        infill_acc = ReconMetricsAccumulator((0.5,), device=device)
     if isinstance(latent_rolls, bool) or int(latent_rolls) != latent_rolls or latent_rolls < 0:
         raise ValueError(f"latent_rolls must be an integer >= 0, got {latent_rolls}")
     model.eval()
@@ -757,6 +781,9 @@ def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nl
             attr_counters.append(roll_attributes(stimuli[:k].float(), getattr(model, "attr_threshold", 0.5)))
             attr_n += k
         rec = output["output"]
+        if infill_acc is not None:      # (after everything that reads this batch's forward out of the model)
+            clean = stimuli if stimuli.dtype == torch.float32 else stimuli.float()
+            infill_acc.update(infill(model, clean, it0, it1)[1][..., it0:it1], clean[..., it0:it1])
         if music is not None:
             music[0].update(rec.float())
             music[1].update(stimuli.float())
@@ -819,6 +846,10 @@ def evaluate(dataloader, model, device, partition_name="Val", verbosity=1, *, nl
             else:
                 mag = torch.nan_to_num(tau[k].abs(), nan=-1.0)
                 results[f"attr_tau_{name}"] = float(tau[k, int(mag.argmax())])
+    if infill_acc is not None:
+        im = infill_acc.compute()
+        for k in ("f1", "precision", "recall"):
+            results[f"infill_{k}"] = 100.0 * im[k][0]
     if verbosity >= 1:
         print(f"\n{partition_name} evaluation results:")
         for k, v in results.items():

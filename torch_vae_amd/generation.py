@@ -184,3 +184,35 @@ def traverse(model, z, dim, values, threshold=0.5):
         rolls = model._run_decode(zz.view(n * steps, model.latent_dim), train=False)
     counters = roll_attributes(rolls, threshold)
     return rolls.view(n, steps, *rolls.shape[1:]), counters.view(n, steps, -1)
+
+
+def checked_time_span(t0, t1, width: int) -> tuple[int, int]:
+    """(t0, t1) as integers with 0 <= t0 < t1 <= width; ValueError otherwise."""
+    for name, v in (("t0", t0), ("t1", t1)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"{name} must be an integer time step, got {v!r}")
+    if not 0 <= t0 < t1 <= width:
+        raise ValueError(f"need 0 <= t0 < t1 <= {width}, got [{t0}, {t1})")
+    return t0, t1
+
+
+def infill(model, x, t0, t1, *, threshold=None):
+    """Fill the time span ``[t0, t1)`` of the rolls ``x`` [n,1,H,W]: the model encodes x with those columns zeroed - what a model
+    trained on ``denoise_span`` corruptions saw - and decodes the posterior mean (running statistics, eval mode, the model
+    untouched, no noise drawn).  Returns ``(filled, xhat)``: ``filled`` is x outside the span, bit for bit, and inside it the
+    reconstruction - binarised to 0/1 at ``threshold`` when one is given - and ``xhat`` the raw reconstruction of the whole roll.
+    Nothing is read back."""
+    model._check_input(x)
+    t0, t1 = checked_time_span(t0, t1, x.shape[-1])
+    if threshold is not None and (isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or not math.isfinite(threshold)):
+        raise ValueError(f"threshold must be None or a finite number, got {threshold!r}")
+    x = x.detach().contiguous().float()
+    masked = x.clone()
+    masked[..., t0:t1] = 0.0
+    with torch.no_grad():
+        mu, _, _ = model._run_encode(masked, train=False)
+        xhat = model._run_decode(mu, train=False)
+    inside = xhat[..., t0:t1]
+    filled = x.clone()
+    filled[..., t0:t1] = inside if threshold is None else (inside >= _f32(threshold)).to(torch.float32)
+    return filled, xhat

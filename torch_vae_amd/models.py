@@ -204,10 +204,10 @@ class _VAEForward(torch.autograd.Function):
     """forward (models.py:185-188) + backward (train.py:650) through the C ABI."""
 
     @staticmethod
-    def forward(ctx, x, anchor, model, eps):
+    def forward(ctx, x, anchor, model, eps, target=None):
         ctx.set_materialize_grads(False)
         ctx.model_ref = weakref.ref(model)      # no model -> _last -> grad_fn -> model reference cycle
-        out = model._run_forward(x, eps, train=model.training)
+        out = model._run_forward(x, eps, train=model.training, target=target)
         ctx.generation = model._fwd_count       # the activations saved for backward live in the context, not in the graph
         handle = torch.zeros((), device=x.device, dtype=torch.float32)
         return (*out, handle)
@@ -217,9 +217,9 @@ class _VAEForward(torch.autograd.Function):
         model = _graph_model(ctx)
         if model._last["train"] and not ctx.needs_input_grad[0]:
             model._run_backward(g_xhat, g_mu, g_lv, g_z, g_pre, g_handle)     # the training path: vae_backward, as always
-            return None, None, None, None
+            return None, None, None, None, None
         dx, _ = model._run_backward_ex(g_xhat, g_mu, g_lv, g_z, g_pre, g_handle, want_dx=ctx.needs_input_grad[0])
-        return dx, None, None, None
+        return dx, None, None, None, None     # (the reconstruction target is data: no gradient flows to it)
 
 
 def _graph_model(ctx):
@@ -601,6 +601,22 @@ class VanillaVAE(nn.Module):
         if x.device != self._flat.device:
             raise RuntimeError("input and model are on different devices")
 
+    def _checked_target(self, target: Tensor | None, x: Tensor):
+        """The reconstruction target of a step whose input is x (denoising: x is the corruption, target the clean roll): checked
+        like x, and as the float32 contiguous tensor the library reads.  None stays None - the target is then x itself."""
+        if target is None:
+            return None
+        self._check_input(target)
+        if target.shape != x.shape or target.device != x.device:
+            raise RuntimeError(f"target must have the input's shape and device: {tuple(target.shape)} on {target.device} against "
+                               f"{tuple(x.shape)} on {x.device}")
+        return target.detach().contiguous().float()
+
+    def _set_recon_target(self, ctx, target: Tensor | None):
+        """vae_set_recon_target for the forward that follows (one-shot in the library).  Inside the device guard.  Nothing without one."""
+        if target is not None:
+            _lib.check(_lib.lib().vae_set_recon_target(ctx.handle, target.data_ptr()), "vae_set_recon_target")
+
     def _noise_seed(self, counter: int) -> int:
         """Seed of the device-side noise (used when no eps is given): distinct per call AND per rank, so data-parallel
         replicas draw independent noise like the reference's per-process torch generator (models.py:182)."""
@@ -622,8 +638,10 @@ class VanillaVAE(nn.Module):
         _lib.check(_lib.lib().vae_pre_latents(ctx.handle, pre.data_ptr(), self._stream()), "vae_pre_latents")
         return pre
 
-    def _run_forward(self, x: Tensor, eps: Tensor | None, train: bool, want_pre: bool | None = None, defer_output: bool = False):
+    def _run_forward(self, x: Tensor, eps: Tensor | None, train: bool, want_pre: bool | None = None, defer_output: bool = False,
+                     target: Tensor | None = None):
         self._check_input(x)
+        target = self._checked_target(target, x)
         x = x.detach().contiguous().float()
         B, L, dev = x.shape[0], self.latent_dim, x.device
         ctx = self._context(B)
@@ -635,12 +653,14 @@ class VanillaVAE(nn.Module):
         self._fwd_count += 1
         seed = self._noise_seed(self._fwd_count)
         with self._device_guard():
+            self._set_recon_target(ctx, target)
             _lib.check(_lib.lib().vae_forward(
                 ctx.handle, x.data_ptr(), B, self._flat.data_ptr(), self._bnflat.data_ptr(), self._nbt.data_ptr(),
                 _lib.ptr(eps), seed, (2 if (train and defer_output) else int(train)), xhat.data_ptr(), mu.data_ptr(),
                 lv.data_ptr(), z.data_ptr(), self._stream()), "vae_forward")
             pre = self._pre_latents(ctx, B, dev, self.materialize_pre_latents if want_pre is None else want_pre)
-        self._last = dict(kind="forward", x=x, xhat=xhat, mu=mu, lv=lv, z=z, train=train, B=B)
+        # (target: kept alive as long as x - a deferred output conv reads it in the backward)
+        self._last = dict(kind="forward", x=x, xhat=xhat, mu=mu, lv=lv, z=z, train=train, B=B, target=target)
         return xhat, mu, lv, z, pre
 
     def _run_encode(self, x: Tensor, train: bool):
@@ -864,7 +884,10 @@ class VanillaVAE(nn.Module):
         std = torch.exp(0.5 * log_var)
         return torch.randn_like(std) * std + mu
 
-    def forward(self, x: Tensor) -> ModelOutput:
+    def forward(self, x: Tensor, target: Tensor | None = None) -> ModelOutput:
+        """models.py:185-188.  ``target`` (default: x itself): what the reconstruction term is taken against - the clean roll of a
+        denoising step whose input x is its corruption (denoise.corrupt_rolls).  It becomes ``ModelOutput["input"]``, so loss() on
+        the output scores the reconstruction against it, on the same HIP path as without one."""
         self._require_device()
         eps, self._next_eps = self._next_eps, None
         if eps is None:
@@ -872,13 +895,13 @@ class VanillaVAE(nn.Module):
             eps = torch.randn(x.shape[0], self.latent_dim, device=x.device, dtype=torch.float32)
         if torch.is_grad_enabled() and (self.training or self._needs_graph(x)):
             anchor = self._anchor_tensor(x.device)
-            xhat, mu, lv, z, pre, handle = _VAEForward.apply(x, anchor, self, eps)
+            xhat, mu, lv, z, pre, handle = _VAEForward.apply(x, anchor, self, eps, target)
         else:
-            xhat, mu, lv, z, pre = self._run_forward(x, eps, train=self.training)
+            xhat, mu, lv, z, pre = self._run_forward(x, eps, train=self.training, target=target)
             handle = None
-        self._last.update(handle=handle, out_ref=xhat, mu=mu, lv=lv, z=z)
+        self._last.update(handle=handle, out_ref=xhat, mu=mu, lv=lv, z=z, target_ref=target)
         encoding = EncoderOutput(mu=mu, log_var=lv, pre_latents=pre)
-        return ModelOutput(output=xhat, input=x, encoded=encoding, latents=z)
+        return ModelOutput(output=xhat, input=x if target is None else target, encoded=encoding, latents=z)
 
     def _anchor_tensor(self, dev):
         a = getattr(self, "_anchor", None)
@@ -890,9 +913,11 @@ class VanillaVAE(nn.Module):
     def loss(self, output: ModelOutput):
         """models.py:190-225."""
         last = self._last
+        # (a forward with a target put the target into output["input"]: the library scored the reconstruction against it)
+        scored = None if last is None else (last.get("target_ref") if last.get("target_ref") is not None else last.get("x"))
         own = (last is not None and output["output"] is last.get("out_ref") and last.get("handle") is not None
-               and output["encoded"]["mu"] is last["mu"] and (output["input"] is last["x"] or
-                                                            output["input"].data_ptr() == last["x"].data_ptr()))
+               and output["encoded"]["mu"] is last["mu"] and (output["input"] is scored or
+                                                            output["input"].data_ptr() == scored.data_ptr()))
         if own:
             loss, out3 = _FusedELBO.apply(last["handle"], self, self.kld_weight)
         elif last is not None and output["output"] is last.get("out_ref") and last.get("handle") is None:
@@ -1007,25 +1032,27 @@ class VanillaVAE(nn.Module):
 
     # -- fused step (no autograd): forward, ELBO, backward in one call chain --
     def fused_forward_backward(self, x: Tensor, eps: Tensor | None = None, use_device_eps: bool = True,
-                               on_decoder_grads=None):
+                               on_decoder_grads=None, target: Tensor | None = None):
         """forward -> loss -> backward (train.py:634-650) with gradients written straight into the
         flat gradient buffer.  Returns a 3-element device tensor {loss, reconstruction, kld_loss}.
         ``on_decoder_grads`` (data parallel): called between the two halves of the backward, when every
         decoder / final_layer gradient is complete in stream order - the caller starts that bucket's
-        all-reduce there so it overlaps the encoder half."""
+        all-reduce there so it overlaps the encoder half.  ``target``: the reconstruction target where it is not x (forward())."""
         self._require_device()
         if eps is None and not use_device_eps:
             eps = torch.randn(x.shape[0], self.latent_dim, device=x.device, dtype=torch.float32)
         # train = 2: the library may leave the output conv / sigmoid / BCE to the backward (one kernel for the layer's
         # forward and backward): xhat and the ELBO scalars are then written by the backward call below
         attr = self._attr_setting(x.shape[0])    # (None: not one launch or byte below differs from the step without the option)
-        xhat, mu, lv, z, _ = self._run_forward(x, eps, train=True, want_pre=False, defer_output=True)
+        xhat, mu, lv, z, _ = self._run_forward(x, eps, train=True, want_pre=False, defer_output=True, target=target)
         g_z = 0
         if attr is not None:
             # the regulariser of this forward's own z, in line on the caller's stream: two small launches whose gradient the
             # backward's latent kernel needs (csrc/edge_kernels.cuh: LatentBwdArgs::gz)
             ids, dims, aw, delta, th = attr
-            self._attr_loss, g = attribute_regularizer(z, roll_attributes(self._last["x"], th), ids, dims, delta, aw)
+            # (the attribute belongs to the phrase, not to its corruption: counted on the target where there is one)
+            scored = self._last["x"] if self._last["target"] is None else self._last["target"]
+            self._attr_loss, g = attribute_regularizer(z, roll_attributes(scored, th), ids, dims, delta, aw)
             g_z = g.data_ptr()
         out3 = torch.empty(3, device=x.device, dtype=torch.float32)
         # the ELBO scalars are only read after the step: finalised beside the backward (joined by it), not in front of it
@@ -1066,14 +1093,17 @@ class VanillaVAE(nn.Module):
 
 
     # -- the whole training step as ONE library call ------------------------------------------------------------
-    def fused_train_step(self, optimizer, x: Tensor, eps: Tensor | None = None, use_device_eps: bool = True, exchange: int = 0):
+    def fused_train_step(self, optimizer, x: Tensor, eps: Tensor | None = None, use_device_eps: bool = True, exchange: int = 0,
+                         target: Tensor | None = None):
         """forward -> ELBO -> backward -> [gradient exchange] -> AdamW (train.py:634-656) enqueued by ONE call into the library
         (include/vae_step.h: vae_train_step_fused) instead of five, with no per-step tensor allocation: the outputs live in
         buffers owned by the model for the batch size, valid until the next fused step of this model.  ``exchange``: 0 none,
         1 one RCCL group between backward and AdamW, 2 bucketed (decoder bucket under the encoder backward, each group's AdamW
-        behind its own bucket) - both need the library communicator.  Returns (out3, xhat)."""
+        behind its own bucket) - both need the library communicator.  ``target``: the reconstruction target where it is not x
+        (forward()).  Returns (out3, xhat)."""
         import ctypes as C
         self._check_input(x)
+        target = self._checked_target(target, x)
         if not x.is_contiguous() or x.dtype != torch.float32:
             x = x.detach().contiguous().float()
         B, L, dev = x.shape[0], self.latent_dim, x.device
@@ -1093,6 +1123,7 @@ class VanillaVAE(nn.Module):
         clip = optimizer._clip_args()   # (max_grad_norm / skip_nonfinite: norm, decision and step count on the device)
         self._bwd_kld_weight = float(self.kld_weight)
         with self._device_guard():
+            self._set_recon_target(ctx, target)
             if clip is not None:
                 _lib.check(_lib.lib().vae_train_step_fused_clipped(
                     ctx.handle, x.data_ptr(), B, self._flat.data_ptr(), self._gflat.data_ptr(), optimizer._m.data_ptr(),
@@ -1107,7 +1138,7 @@ class VanillaVAE(nn.Module):
                     n, offs, sizes, lrs, b1s, beta2, adam_eps, wd, float(optimizer.grad_scale), optimizer._step + 1, int(exchange),
                     xhat.data_ptr(), mu.data_ptr(), lv.data_ptr(), z.data_ptr(), out3.data_ptr(), self._stream()), "vae_train_step_fused")
         optimizer._stepped()
-        self._last = dict(kind="forward", x=x, xhat=xhat, mu=mu, lv=lv, z=z, train=True, B=B)
+        self._last = dict(kind="forward", x=x, xhat=xhat, mu=mu, lv=lv, z=z, train=True, B=B, target=target)
         params, views = self._param_grad_views()
         if params[0].grad is not views[0] or params[-1].grad is not views[-1]:   # (bound once: the fused path never unbinds them)
             self.bind_flat_grads()

@@ -21,6 +21,7 @@ import torch
 import torch.distributed as dist
 
 from .data import DevicePianorollLoader
+from .denoise import Corruption
 from .models import VanillaVAE
 from .optim import FusedAdamW
 
@@ -140,7 +141,7 @@ def _refuse_overlap_on_eight_queues():
                            "VAE_DP_OVERLAP=1, which selects 6) before the process starts, or use the default in-line exchange")
 
 
-def fused_step(model: VanillaVAE, optimizer, x, eps=None, use_device_eps: bool = True, overlap: bool | None = None):
+def fused_step(model: VanillaVAE, optimizer, x, eps=None, use_device_eps: bool = True, overlap: bool | None = None, target=None):
     """One training step on the fused path (train.py:634-656): forward, ELBO, backward, [gradient all-reduce], AdamW.
     Data parallel (the product path on a multi-GPU node): by default both gradient buckets go out as ONE RCCL group
     through the library's communicator on the compute stream, between the last backward kernel and the AdamW kernel
@@ -148,7 +149,9 @@ def fused_step(model: VanillaVAE, optimizer, x, eps=None, use_device_eps: bool =
     decoder bucket's all-reduce on the context's communication stream between the two halves of the backward, under
     the encoder half, the encoder bucket following in line; measured here that costs more than the ~40 us it can hide
     (+70 us with six hardware queues: event hand-offs and a sixth stream; with eight queues the whole step runs 2.5x
-    slower, which this function refuses), so it is opt-in: ``overlap=True`` or VAE_DP_OVERLAP=1."""
+    slower, which this function refuses), so it is opt-in: ``overlap=True`` or VAE_DP_OVERLAP=1.
+    ``target``: the reconstruction target where it is not x - the clean roll of a denoising step (denoise.corrupt_rolls); every
+    path below takes it."""
     one_call = isinstance(optimizer, FusedAdamW) and os.environ.get("VAE_ONE_CALL_STEP", "1") != "0"
     if getattr(model, "attr_reg", None) is not None:
         one_call = False      # the attribute regulariser sits between forward and backward: the split path (the one-call step has no such hook)
@@ -157,8 +160,8 @@ def fused_step(model: VanillaVAE, optimizer, x, eps=None, use_device_eps: bool =
         one_call = optimizer._model is model and len(optimizer.param_groups) == len(optimizer._ranges)
     if not _dist_active():
         if one_call:   # the whole step in one library call (include/vae_step.h: vae_train_step_fused)
-            return model.fused_train_step(optimizer, x, eps=eps, use_device_eps=use_device_eps, exchange=0)
-        out3, xhat = model.fused_forward_backward(x, eps=eps, use_device_eps=use_device_eps)
+            return model.fused_train_step(optimizer, x, eps=eps, use_device_eps=use_device_eps, exchange=0, target=target)
+        out3, xhat = model.fused_forward_backward(x, eps=eps, use_device_eps=use_device_eps, target=target)
     else:
         if overlap is None:
             overlap = os.environ.get("VAE_DP_OVERLAP", "0") == "1"
@@ -168,13 +171,13 @@ def fused_step(model: VanillaVAE, optimizer, x, eps=None, use_device_eps: bool =
             model._context(x.shape[0])   # (creates the context - and with it the library's communicator - on the first step)
         if one_call and model.library_comm_world() == _dp_world():
             # data parallel through the library's communicator: in-line group (1) or bucketed exchange (2) inside the same call
-            return model.fused_train_step(optimizer, x, eps=eps, use_device_eps=use_device_eps, exchange=2 if overlap else 1)
+            return model.fused_train_step(optimizer, x, eps=eps, use_device_eps=use_device_eps, exchange=2 if overlap else 1, target=target)
         if overlap:
-            out3, xhat = model.fused_forward_backward(x, eps=eps, use_device_eps=use_device_eps,
+            out3, xhat = model.fused_forward_backward(x, eps=eps, use_device_eps=use_device_eps, target=target,
                                                       on_decoder_grads=lambda: _reduce(model, ("decoder",), on_comm_stream=True))
             _reduce(model, ("encoder",))
         else:
-            out3, xhat = model.fused_forward_backward(x, eps=eps, use_device_eps=use_device_eps)
+            out3, xhat = model.fused_forward_backward(x, eps=eps, use_device_eps=use_device_eps, target=target)
             _reduce(model, ("decoder", "encoder"))
     optimizer.step()
     return out3, xhat
@@ -315,6 +318,11 @@ def train_one_epoch(config, model, optimizer, scheduler, criterion, dataloader, 
         model.attr_weight = config.attr_weight
     if getattr(config, "attr_delta", None) is not None:
         model.attr_delta = config.attr_delta
+    # denoising objective (optional config fields; none of them: exactly the loop without it): the batch is the target, its corruption
+    # the input.  Roll b of the step at total_step has the counter (total_step * world + rank) * B + b: the draws are a function of
+    # the step, so a resumed run continues them
+    corruption = Corruption.from_config(config) if isinstance(model, VanillaVAE) else None
+    rank = dist.get_rank() if _dist_active() else 0
     if isinstance(dataloader, DevicePianorollLoader):   # its order and augmentation draws are functions of (seed, epoch)
         dataloader.set_epoch(epoch)
     n_batches = len(dataloader)
@@ -341,12 +349,18 @@ def train_one_epoch(config, model, optimizer, scheduler, criterion, dataloader, 
             model.kld_weight = kl_schedule.value(total_step)
             if kl_schedule.capacity_max is not None:
                 model.kl_capacity = kl_schedule.capacity(total_step)
+        clean = None
+        if corruption is not None:
+            clean, stimuli = stimuli, corruption(stimuli, counter0=(total_step * world + rank) * batch_size_this_gpu)
         if fused:
             # train.py:634-656 as one HIP chain: forward, ELBO, backward, [all-reduce], AdamW
-            out3, reconstruction = fused_step(model, optimizer, stimuli, use_device_eps=False)
+            if clean is None:
+                out3, reconstruction = fused_step(model, optimizer, stimuli, use_device_eps=False)
+            else:
+                out3, reconstruction = fused_step(model, optimizer, stimuli, use_device_eps=False, target=clean)
         else:
             with torch.no_grad() if getattr(config, "freeze_encoder", False) else nullcontext():
-                output = model.forward(stimuli)
+                output = model.forward(stimuli) if clean is None else model.forward(stimuli, target=clean)
                 reconstruction = output["output"]
             optimizer.zero_grad()
             loss_output = criterion(output)
