@@ -20,7 +20,7 @@ from .types_helpers import EncoderOutput, LossOutput, ModelOutput  # noqa: F401,
 __all__ = ["VanillaVAE", "FusedAdamW", "train_one_epoch", "build_optimizer", "SyntheticPianorollLoader", "PianorollDataset",
            "DevicePianorollLoader", "epoch_indices", "gather_rolls", "augmentation_params", "extract_notes", "binarize_rolls",
            "events_to_lists", "nearest_rolls", "novelty_summary", "sample_novelty", "compare_encodings", "sample_fidelity",
-           "corrupt_rolls", "corruption_spans", "infill"]
+           "corrupt_rolls", "corruption_spans", "infill", "WeightAverage"]
 
 
 def __getattr__(name):
@@ -51,6 +51,9 @@ def __getattr__(name):
     if name in ("corrupt_rolls", "corruption_spans", "Corruption"):
         from . import denoise
         return getattr(denoise, name)
+    if name == "WeightAverage":
+        from .averaging import WeightAverage
+        return WeightAverage
     if name in ("extract_notes", "binarize_rolls", "events_to_lists", "interpolate_latents", "infill"):
         from . import generation
         return getattr(generation, name)

@@ -1,6 +1,7 @@
 """ctypes binding of the C-ABI library (include/vae_step.h, include/vae_mixture.h for the latent mixture, include/vae_music.h
 for the musical statistics, include/vae_fidelity.h for the set-level fidelity metrics, include/vae_attributes.h for the
-attribute-regularised latents and include/vae_denoise.h for the denoising corruption).
+attribute-regularised latents, include/vae_denoise.h for the denoising corruption and include/vae_average.h for the weight
+averaging).
 
 The product path has no CPU fallback: if the HIP library is missing this module
 raises at import of the first symbol, loudly.
@@ -57,6 +58,9 @@ ATTR_MAX_PAIRS, ATTR_MAX_BATCH, ATTR_MAX_DIM, ATTR_MAX_ROWS, ATTR_MAX_CELLS, ATT
 # include/vae_denoise.h: the counter-generator streams of note dropout, the time span and the spurious cells; the limits on h and w
 DENOISE_STREAM_DROP, DENOISE_STREAM_SPAN, DENOISE_STREAM_ADD = 902, 903, 904
 DENOISE_MAX_ROWS, DENOISE_MAX_COLS = 1 << 20, 1 << 20
+# include/vae_average.h: the kinds of average; the bytes of the device state (int64 seen_step | int64 n_averaged | f64 last_weight | reserved)
+AVG_EMA, AVG_EQUAL = 0, 1
+AVG_STATE_BYTES = 32
 
 PARAM_NAMES = (
     [f"encoder.{i}.{j}" for i in range(4) for j in ("0.weight", "0.bias", "1.weight", "1.bias")]
@@ -174,6 +178,10 @@ def lib():
     # include/vae_denoise.h
     _sig(L.vae_denoise_corrupt, i32, [p, p, p, i64, i32, i32, f32, f64, i32, i32, f64, f32, p, u64, u64, u64, p])
     _sig(L.vae_denoise_params, i32, [p, i64, i32, i32, i32, u64, u64, u64, p])
+    # include/vae_average.h
+    _sig(L.vae_average_update, i32, [p, p, i64, f32, p, p, i64, f32, i32, f64, f64, p, p, p])
+    _sig(L.vae_average_swap, i32, [p, p, i64, p, p, i64, p])
+    _sig(L.vae_average_state_init, i32, [p, p, i64, p])
     _lib = L
     return L
 
@@ -206,6 +214,9 @@ ATTR_EXPORTS = ["vae_attr_roll_counters", "vae_attr_regularizer", "vae_attr_conc
 
 # include/vae_denoise.h (and this one)
 DENOISE_EXPORTS = ["vae_denoise_corrupt", "vae_denoise_params"]
+
+# include/vae_average.h (and this one)
+AVERAGE_EXPORTS = ["vae_average_update", "vae_average_swap", "vae_average_state_init"]
 
 
 def check(rc: int, what: str = ""):

@@ -9,6 +9,7 @@ still runs through the same kernels via autograd.  With ``torch.distributed`` in
 (one process per GPU, RCCL) the optimised gradient ranges are all-reduced before the update
 -- plain data parallelism, which the reference only prepares for (train.py:165-166,201,663).
 ``KLSchedule`` moves ``model.kld_weight`` (and a KL capacity target) per step when the config asks for it.
+``config.weight_average`` keeps an EMA / SWA of the weights beside the step (``averaging.WeightAverage``, ``model.weight_average``).
 """
 from __future__ import annotations
 
@@ -20,6 +21,7 @@ from contextlib import nullcontext
 import torch
 import torch.distributed as dist
 
+from .averaging import WeightAverage
 from .data import DevicePianorollLoader
 from .denoise import Corruption
 from .models import VanillaVAE
@@ -323,6 +325,16 @@ def train_one_epoch(config, model, optimizer, scheduler, criterion, dataloader, 
     # the step, so a resumed run continues them
     corruption = Corruption.from_config(config) if isinstance(model, VanillaVAE) else None
     rank = dist.get_rank() if _dist_active() else 0
+    # weight averaging (optional config field; without it: exactly the loop without it): the model's own WeightAverage, or a fresh one that
+    # takes the optimiser's current step count for seen.  A plain attribute of the model, not a submodule: state_dict() keys stay.  The
+    # schedule is a function of total_step; data-parallel replicas hold the same parameters and skip the same steps, so each averages alone
+    averager = None
+    if getattr(config, "weight_average", None) is not None:
+        averager = getattr(model, "weight_average", None)
+        if averager is None:
+            averager = WeightAverage.from_config(config, model)
+            averager.reset(optimizer)
+            model.weight_average = averager
     if isinstance(dataloader, DevicePianorollLoader):   # its order and augmentation draws are functions of (seed, epoch)
         dataloader.set_epoch(epoch)
     n_batches = len(dataloader)
@@ -376,6 +388,8 @@ def train_one_epoch(config, model, optimizer, scheduler, criterion, dataloader, 
             grad_norm = optimizer.last_grad_norm
         scheduler.step()
         total_step += 1
+        if averager is not None and averager.due(total_step):
+            averager.update(optimizer)    # (a FusedAdamW's device step count gates it: a skipped step is not averaged, nothing is read back)
         batch_size_all = batch_size_this_gpu * getattr(config, "world_size", world)
         n_samples_seen += batch_size_all
         # The reference reads the three scalars with .item() every step (train.py:672-674), i.e. one host-device round trip

@@ -72,6 +72,8 @@ def checkpoint_modules(model, optimizer, scheduler, save_all_modules: bool = Fal
         mods.update({name: getattr(model, name) for name in OTHER_MODULES})
     mods["optimizer"] = optimizer
     mods["scheduler"] = scheduler
+    if getattr(model, "weight_average", None) is not None:      # averaging.WeightAverage of a run with config.weight_average
+        mods["weight_average"] = model.weight_average
     return mods
 
 
@@ -89,5 +91,12 @@ def load_checkpoint(model, optimizer, scheduler, checkpoint) -> dict:
         optimizer.load_state_dict(checkpoint["optimizer"])
     if scheduler is not None:
         scheduler.load_state_dict(checkpoint["scheduler"])
+    if "weight_average" in checkpoint:      # (after the optimiser: its restored device step count is the one the average has seen)
+        from .averaging import WeightAverage
+        state = checkpoint["weight_average"]
+        if getattr(model, "weight_average", None) is None:
+            model.weight_average = WeightAverage(model, kind=state["kind"], decay=state["decay"], warmup=state["warmup"],
+                                                 use_buffers=bool(state["use_buffers"]))
+        model.weight_average.load_state_dict(state, optimizer)
     return {"total_step": checkpoint.get("total_step", 0), "n_samples_seen": checkpoint.get("n_samples_seen", 0),
             "epoch": checkpoint.get("epoch", 0), "best_epoch": checkpoint.get("best_epoch", 0)}
